@@ -18,12 +18,15 @@ BatchNorm) + PointFlowNLL + backward on a flattened decoder -> ONE all-reduce of
 Adam (lib/networks/training.py:37-56 with the collective between :55 and :56); `--model autoencoder` = the whole
 Local_Cond_RNVP_MC_Global_RNVP_VAE of the workload's YAML (cfg3: 12 972 413 parameters, one 51.9 MB message).  The leg first
 runs 6 steps with graph replay and 6 with eager launches and refuses to report a value if their losses differ.
-The default run also carries `extra.configs`: short legs of L = 63 / 15, cfg3, cfg4 and cfg5 measured in the same process.
+A plain run sets up, warms up, times the K steps and prints the headline line -- nothing else.  `--full` adds what takes runs
+of its own: `roofline` (per-kernel durations), `cpu_baseline` and `parity` (the CPU oracle), `pipelined`, and on the default
+run `extra` (eager launches, the other split precisions, the training step, per-rank proxies and `extra.configs`: short legs
+of L = 63 / 15, cfg3, cfg4 and cfg5 measured in the same process).
+`--dump-outputs DIR` writes, after the timed steps, what the timed path returned in its last step as DIR/<name>.npy (rank 0).
 
 N GPUs: one process per GPU.  `--gpus N` without a torchrun environment starts the N ranks itself (children are
 created before this process touches the GPU); under `python -m torch.distributed.run` the ranks read
-RANK/LOCAL_RANK/WORLD_SIZE.  value = all ranks' points / max-over-ranks time.  Rank 0 prints ONE JSON line carrying
-`roofline`, `cpu_baseline` and `parity`.
+RANK/LOCAL_RANK/WORLD_SIZE.  value = all ranks' points / max-over-ranks time.  Rank 0 prints ONE JSON line.
 """
 import argparse
 import ctypes
@@ -74,7 +77,7 @@ def parse(argv=None):
                     help="STRONG scaling of a per-GPU config (cfg2 / cfg4): the config's 32 clouds are the GLOBAL batch, sharded "
                          "over the ranks (4 per rank at 8 GPUs) -- what an 8-GPU job does to BASELINE's B=32; the default line is "
                          "weak scaling (32 clouds per rank)")
-    ap.add_argument("--no-proxy", action="store_true", help="skip `extra.per_rank_proxy` of the default run")
+    ap.add_argument("--no-proxy", action="store_true", help="with --full: skip `extra.per_rank_proxy` of the default run")
     ap.add_argument("--points", type=int, default=None)
     ap.add_argument("--layers", type=int, default=None, help="coupling layers: 14 (BASELINE metric), 15, 63; train leg default 63")
     ap.add_argument("--latent", type=int, default=None)
@@ -90,13 +93,19 @@ def parse(argv=None):
     ap.add_argument("--streams", type=int, default=1,
                     help="consecutive steps go round-robin over this many streams (each with its own buffers); 1 (default) = "
                          "strictly one after another, the regime the roofline numbers and the committed profiles describe")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: roofline / per-kernel durations, CPU baseline "
+                         "and parity against the CPU oracle, `pipelined`, and the `extra` legs of the default run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                         "(float32, or float64 for integer and float64 arrays; at most 64 MB in all)")
     ap.add_argument("--pipelined", type=int, default=3,
-                    help="with --streams 1: also report (outside the timed region, as `pipelined`) the throughput with this many "
-                         "steps in flight; 0 = skip")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra legs of the default run (bf16x6, eager, train step)")
-    ap.add_argument("--no-configs", action="store_true", help="skip `extra.configs` (the short legs of the other workloads) of the default run")
-    ap.add_argument("--train-steps", type=int, default=20, help="timed steps of the `extra.train_step` leg")
+                    help="with --streams 1 and --full: also report (outside the timed region, as `pipelined`) the throughput with "
+                         "this many steps in flight; 0 = skip")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the timed CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra legs of the default run (bf16x6, eager, train step)")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip `extra.configs` (the short legs of the other workloads) of the default run")
+    ap.add_argument("--train-steps", type=int, default=20, help="timed steps of the `extra.train_step` leg (--full)")
     ap.add_argument("--model", default=None, choices=["decoder", "encoder", "autoencoder"],
                     help="train leg: decoder = the flow decoder on given codes (default), encoder = PointNet encoder + code head + "
                          "decoder, autoencoder = the whole Local_Cond_RNVP_MC_Global_RNVP_VAE of the workload's YAML (cfg3: "
@@ -344,6 +353,26 @@ def device_clock_mhz():
         return int(torch.cuda.clock_rate())
     except Exception:
         return None
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: `arrays` (name -> tensor) as directory/<name>.npy, so that two builds can be compared output for output.
+    float32 stays float32; float64 and integer arrays (indices) are written as float64, exactly.  An array larger than its
+    equal share of the 64 MB budget is written as a fixed, seeded sample of its flattened elements (sorted positions), the
+    same positions in every run of the same arguments."""
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        a = a.astype(np.float32 if a.dtype in (np.float32, np.float16, np.bool_) else np.float64)
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            pos = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[pos]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def clouds_of_rank(args, rank, world):
@@ -595,28 +624,34 @@ def leg_eval(args, rank, world, dist, device):
 
     # Every step is one full pass over one batch.  With --streams S > 1 consecutive steps go round-robin over S streams, each
     # stream with its own captured graph and therefore its own intermediate / output buffers.
+    full = getattr(args, "full", False)
     S = max(1, args.streams)
-    S_all = max(S, args.pipelined if S == 1 else 0)
+    S_all = max(S, args.pipelined if (S == 1 and full) else 0)
     streams = [torch.cuda.Stream() for _ in range(S_all)]
     G = max(1, args.graph_steps) if (S == 1 and not args.no_graph) else 1     # multi-step graphs only in the one-stream regime
     runners, multi = [], None
-    for st in streams:
+    outs, multi_out = [], None           # what each runner's step returns (a graph's outputs are its own static buffers)
+    for i, st in enumerate(streams):
         st.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(st):
             out = step()
         torch.cuda.synchronize()
+        outs.append(out)
         if args.no_graph:
-            runners.append(step)
+            def eager(i=i):
+                outs[i] = step()
+            runners.append(eager)
         else:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, stream=st):
                 out = step()
+            outs[i] = out
             runners.append(graph.replay)
             if G > 1 and multi is None:
                 multi = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(multi, stream=st):
                     for _ in range(G):
-                        out = step()
+                        multi_out = step()
 
     def run_steps(n, S=S):
         if multi is not None and S == 1:
@@ -633,6 +668,10 @@ def leg_eval(args, rank, world, dist, device):
     run_steps(args.settle)
     elapsed, elapsed_wall = timed_region(run_steps, args, dist, device, launch_streams=streams[:S])
     sclk = device_clock_mhz()            # right behind the timed region: the shader clock the steps ran at (boxes differ)
+    # the outputs of the last timed step: the one-step graph that ran last, or the multi-step graph's last step
+    out = multi_out if (multi is not None and S == 1 and args.steps % G == 0) else outs[(args.steps - 1) % S]
+    if rank == 0 and getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, dict(zip(("points", "sum_logvar", "dist1", "idx1", "dist2", "idx2", "chamfer_per_cloud"), out)))
 
     pipelined = None
     if S_all > S:                        # the same steps with S_all of them in flight, reported beside the headline
@@ -647,15 +686,39 @@ def leg_eval(args, rank, world, dist, device):
     assert torch.isfinite(p_out).all() and torch.isfinite(cd).all() and (d1 >= 0).all()
 
     extra = {}
-    if not args.no_extra and not args.no_graph and S == 1:
+    if full and not args.no_extra and not args.no_graph and S == 1:
         extra = eval_extras(args, dec, z, g, tgt_pm, L, step, streams[0])
     if rank != 0:
         return None, extra
+    from dpf_nets_amd.metrics.StructuralLosses import StructuralLossesBackend as BK
     B, N = batch, args.points
     pts_per_step = args.points * global_clouds
+    cfg = CONFIGS[args.config]
+    line = {
+        "metric": "points/sec through %d-layer flow + Chamfer, B=%d N=%d" % (L, B, N),
+        "value": pts_per_step / (elapsed / args.steps), "unit": "points/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+        "scaling": ("strong" if getattr(args, "strong", False) else cfg["scaling"]) if args.batch is None else "weak", "vs_baseline": None,
+        "dtype": args.precision + " MFMA operands, fp32 accumulate/points",
+        "data": "synthetic",
+        "config": {"workload": "%s: %d coupling layers (first %d of LocalCondRNVPDecoder(n_flows=%d)), direct/eval-BN, + "
+                               "nn_distance both directions + CD reduction" % (cfg["name"], L, L, n_flows),
+                   "clouds_per_gpu": B, "points_per_cloud": N, "hidden": 64, "latent": args.latent,
+                   "global_clouds": pts_per_step // N, "per_layer_lists": bool(args.lists),
+                   "launch": ("eager" if args.no_graph else "hipGraph replay, %d step(s) per graph" % G) +
+                   (", consecutive steps round-robin over %d streams with their own buffers" % S if S > 1 else ""),
+                   "steps_in_flight": S, "settle_steps": args.settle, "parallelism": "clouds sharded, no collective",
+                   "timing": "HIP events on the launch stream around the K steps (ms_per_step); host clock around the same "
+                             "steps + synchronize beside it (ms_per_step_wall)",
+                   "ms_per_step_wall": elapsed_wall / args.steps * 1e3, "sclk_mhz": sclk,
+                   "chamfer_impl": BK.NN_IMPL + (" (matrix-core filtered exact search at this size)" if BK.NN_IMPL == "auto" and
+                                                 2.0 * B * N * N >= 1e8 and B * 2 * ((N + 255) // 256) >= 64 else "")},
+        "device": {"name": torch.cuda.get_device_name(device), "sclk_mhz_behind_timed_region": sclk},
+    }
+    if not full:
+        return line, extra
     kt_alone = kernel_timings(dec, z, g, tgt_pm, L, args.precision)
     kt = kernel_timings_in_flight(dec, z, g, tgt_pm, L, args.precision, S) if S > 1 else kt_alone
-    from dpf_nets_amd.metrics.StructuralLosses import StructuralLossesBackend as BK
     from dpf_nets_amd._lib import lib as _dpf_lib
     n16 = _dpf_lib().dpf_flow_tile16_launches()
     step()
@@ -696,29 +759,8 @@ def leg_eval(args, rank, world, dist, device):
     # bf16 MFMA per 32x32 of them and evaluates the exact formula only for the candidates that can still win
     roof["chamfer_equiv_fp32_tflops"] = 8.0 * roof["chamfer_pair_evals_per_s"] / 1e12
     roof["chamfer_equiv_frac_of_fp32_valu_peak"] = roof["chamfer_equiv_fp32_tflops"] / 157.3
-    cfg = CONFIGS[args.config]
-    line = {
-        "metric": "points/sec through %d-layer flow + Chamfer, B=%d N=%d" % (L, B, N),
-        "value": pts_per_step / (elapsed / args.steps), "unit": "points/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-        "scaling": ("strong" if getattr(args, "strong", False) else cfg["scaling"]) if args.batch is None else "weak", "vs_baseline": None,
-        "dtype": args.precision + " MFMA operands, fp32 accumulate/points",
-        "data": "synthetic",
-        "config": {"workload": "%s: %d coupling layers (first %d of LocalCondRNVPDecoder(n_flows=%d)), direct/eval-BN, + "
-                               "nn_distance both directions + CD reduction" % (cfg["name"], L, L, n_flows),
-                   "clouds_per_gpu": B, "points_per_cloud": N, "hidden": 64, "latent": args.latent,
-                   "global_clouds": pts_per_step // N, "per_layer_lists": bool(args.lists), "flow_kernel": flow_name,
-                   "launch": ("eager" if args.no_graph else "hipGraph replay, %d step(s) per graph" % G) +
-                   (", consecutive steps round-robin over %d streams with their own buffers" % S if S > 1 else ""),
-                   "steps_in_flight": S, "settle_steps": args.settle, "parallelism": "clouds sharded, no collective",
-                   "timing": "HIP events on the launch stream around the K steps (ms_per_step); host clock around the same "
-                             "steps + synchronize beside it (ms_per_step_wall)",
-                   "ms_per_step_wall": elapsed_wall / args.steps * 1e3, "sclk_mhz": sclk,
-                   "chamfer_impl": BK.NN_IMPL + (" (matrix-core filtered exact search at this size)" if BK.NN_IMPL == "auto" and
-                                                 2.0 * B * N * N >= 1e8 and B * 2 * ((N + 255) // 256) >= 64 else "")},
-        "roofline": roof,
-        "device": {"name": torch.cuda.get_device_name(device), "sclk_mhz_behind_timed_region": sclk},
-    }
+    line["config"]["flow_kernel"] = flow_name
+    line["roofline"] = roof
     if pipelined is not None:
         line["pipelined"] = {
             "steps_in_flight": S_all, "value": batch * args.points / pipelined,
@@ -800,13 +842,27 @@ def leg_cfg5(args, rank, world, dist, device):
 
     out = step()
     torch.cuda.synchronize()
+    last = [out]
 
     def run_steps(n):
         for _ in range(n):
-            step()
+            last[0] = step()
     elapsed, elapsed_wall = timed_region(run_steps, args, dist, device)
     if rank != 0:
         return None, {}
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, dict(zip(("dist1", "idx1", "dist2", "idx2", "chamfer_per_cloud", "match_cost"), last[0])))
+    line = {"metric": "points/sec through Chamfer + approx-EMD, B=%d N=M=%d" % (batch, N),
+            "value": global_clouds * N / (elapsed / args.steps), "unit": "points/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+            "scaling": "strong" if args.batch is None else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": CONFIGS["cfg5"]["name"] + ": nn_distance both directions + CD reduction + match_cost "
+                                   "(approxmatch + matchcost)", "clouds_per_gpu": batch, "points_per_cloud": N,
+                       "global_clouds": global_clouds, "launch": "eager", "parallelism": "clouds sharded, no collective",
+                       "timing": "HIP events on the launch stream (ms_per_step); host clock beside it (ms_per_step_wall)",
+                       "ms_per_step_wall": elapsed_wall / args.steps * 1e3}}
+    if not getattr(args, "full", False):
+        return line, {}
 
     def ev_time(fn, reps=5):
         fn(); torch.cuda.synchronize()
@@ -854,16 +910,7 @@ def leg_cfg5(args, rank, world, dist, device):
             "kernels_us": {"nn_distance": t_nn, "approxmatch_cost": t_emd},
             "chamfer_pair_evals_per_s": 2.0 * batch * N * N / (t_nn * 1e-6),
             "emd_exp_per_s": ach}
-    line = {"metric": "points/sec through Chamfer + approx-EMD, B=%d N=M=%d" % (batch, N),
-            "value": global_clouds * N / (elapsed / args.steps), "unit": "points/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "strong" if args.batch is None else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": CONFIGS["cfg5"]["name"] + ": nn_distance both directions + CD reduction + match_cost "
-                                   "(approxmatch + matchcost)", "clouds_per_gpu": batch, "points_per_cloud": N,
-                       "global_clouds": global_clouds, "launch": "eager", "parallelism": "clouds sharded, no collective",
-                       "timing": "HIP events on the launch stream (ms_per_step); host clock beside it (ms_per_step_wall)",
-                       "ms_per_step_wall": elapsed_wall / args.steps * 1e3},
-            "roofline": roof}
+    line["roofline"] = roof
     base = parity = None
     if world == 1:
         from oracle import structural as S     # the checker / CPU baseline leg
@@ -992,7 +1039,7 @@ def replay_equals_eager(args, rank, device, batch, layers, model_kind, n=6):
     return seqs[0] == seqs[1], replays[0]
 
 
-def train_step_leg(args, rank, world, dist, device, batch, layers, steps, warmup, model_kind=None):
+def train_step_leg(args, rank, world, dist, device, batch, layers, steps, warmup, model_kind=None, dump_dir=None):
     from dpf_nets_amd import networks as nets
     from dpf_nets_amd import distributed as D
     if layers % 3:
@@ -1069,43 +1116,47 @@ def train_step_leg(args, rank, world, dist, device, batch, layers, steps, warmup
     _lib_handle().dpf_train_graph_stats(gstats)          # of the timed region: read before the eager per-kernel pass below
     _lib_handle().dpf_train_colsum_fallbacks.restype = ctypes.c_long
     colsum_fallbacks = int(_lib_handle().dpf_train_colsum_fallbacks())   # (workgroups that gave up waiting for role workgroups)
-    # ---- per-kernel durations of the decoder stack (outside the timed region): HIP events around every launch, eager
+    if dump_dir:                # the last timed step's loss, its (all-reduced) flat gradient and the parameters Adam left
+        dump_outputs(dump_dir, {"loss": loss.detach().reshape(1), "flat_gradient": arena.buf,
+                                "parameters": torch.cat([p.detach().reshape(-1) for p in params])})
+    # ---- per-kernel durations of the decoder stack (outside the timed region, --full): HIP events around every launch, eager
     kernels = None
-    try:
-        L_ = _lib_handle()
-        ksteps = 3
-        us, calls = (ctypes.c_double * 8)(), (ctypes.c_long * 8)()
-        L_.dpf_train_kernel_times(1, None, None)        # turns graph recording / replay off process-wide ...
+    if getattr(args, "full", False):
         try:
-            for _ in range(ksteps):
-                step()
-        finally:
-            L_.dpf_train_kernel_times(0, us, calls)     # ... and only this call restores it: also when a step raises
-        P = batch * N
-        # FLOPs a kernel executes per layer for P points (both branches): conditioner forward 2 x (2*F*|K| + 2*F*F) ~ 16 896 / pt
-        # (|K| ~ 1.5 on average), output layer 2 x 2*|W|*F ~ 384, W1^T dh1 and dh1 h0^T 2 x 2*F*F = 16 384 each
-        fwd, out_l, sq = 16896.0 * P, 384.0 * P, 16384.0 * P
-        flop = {"tstats_h1": fwd, "flow_kernel(L=1)": fwd + out_l, "tbwd1": fwd + out_l, "tbwd2": fwd + 2 * sq, "tfold": 0.0, "tcolsum": 0.0,
-                "tstats_x": 0.0, "tbwd3f": 0.0}
-        names = ["tstats_x", "tstats_h1", "tfold", "flow_kernel(L=1)", "tbwd1", "tbwd2", "tcolsum", "tbwd3f"]
-        kernels, per_layer = {}, 0.0
-        for i, nm in enumerate(names):
-            if calls[i] == 0:
-                continue
-            t_us = us[i] / calls[i]
-            per = us[i] / (ksteps * layers)
-            per_layer += per
-            kernels[nm] = {"us": t_us, "launches_per_step": calls[i] / ksteps, "us_per_layer": per,
-                           "gflop": flop[nm] / 1e9, "tflops": (flop[nm] / (t_us * 1e-6) / 1e12) if flop[nm] else None,
-                           "frac_of_mfma_peak": (flop[nm] / (t_us * 1e-6) / 1e12 / MFMA_BF16_PEAK_TF) if flop[nm] else None}
-        kernels["sum_us_per_layer"] = per_layer
-        kernels["note"] = ("HIP events around every launch of the stack's kernels, %d eager steps (dpf_train_kernel_times): event to "
-                           "event, i.e. kernel duration + the ~1.5 us launch gap of an eager launch -- the rocprofv3 kernel durations of "
-                           "the same command are in profiles/r06_train_kernel_trace.txt; gflop = "
-                           "what the kernel executes per launch incl. the recomputation of the conditioner; tfold / tcolsum / "
-                           "tstats_x / tbwd3f are reductions (latency-bound, no matrix work)" % ksteps)
-    except Exception as e:       # noqa: BLE001
-        kernels = {"error": repr(e)}
+            L_ = _lib_handle()
+            ksteps = 3
+            us, calls = (ctypes.c_double * 8)(), (ctypes.c_long * 8)()
+            L_.dpf_train_kernel_times(1, None, None)        # turns graph recording / replay off process-wide ...
+            try:
+                for _ in range(ksteps):
+                    step()
+            finally:
+                L_.dpf_train_kernel_times(0, us, calls)     # ... and only this call restores it: also when a step raises
+            P = batch * N
+            # FLOPs a kernel executes per layer for P points (both branches): conditioner forward 2 x (2*F*|K| + 2*F*F) ~ 16 896 / pt
+            # (|K| ~ 1.5 on average), output layer 2 x 2*|W|*F ~ 384, W1^T dh1 and dh1 h0^T 2 x 2*F*F = 16 384 each
+            fwd, out_l, sq = 16896.0 * P, 384.0 * P, 16384.0 * P
+            flop = {"tstats_h1": fwd, "flow_kernel(L=1)": fwd + out_l, "tbwd1": fwd + out_l, "tbwd2": fwd + 2 * sq, "tfold": 0.0, "tcolsum": 0.0,
+                    "tstats_x": 0.0, "tbwd3f": 0.0}
+            names = ["tstats_x", "tstats_h1", "tfold", "flow_kernel(L=1)", "tbwd1", "tbwd2", "tcolsum", "tbwd3f"]
+            kernels, per_layer = {}, 0.0
+            for i, nm in enumerate(names):
+                if calls[i] == 0:
+                    continue
+                t_us = us[i] / calls[i]
+                per = us[i] / (ksteps * layers)
+                per_layer += per
+                kernels[nm] = {"us": t_us, "launches_per_step": calls[i] / ksteps, "us_per_layer": per,
+                               "gflop": flop[nm] / 1e9, "tflops": (flop[nm] / (t_us * 1e-6) / 1e12) if flop[nm] else None,
+                               "frac_of_mfma_peak": (flop[nm] / (t_us * 1e-6) / 1e12 / MFMA_BF16_PEAK_TF) if flop[nm] else None}
+            kernels["sum_us_per_layer"] = per_layer
+            kernels["note"] = ("HIP events around every launch of the stack's kernels, %d eager steps (dpf_train_kernel_times): event to "
+                               "event, i.e. kernel duration + the ~1.5 us launch gap of an eager launch -- the rocprofv3 kernel durations of "
+                               "the same command are in profiles/r06_train_kernel_trace.txt; gflop = "
+                               "what the kernel executes per launch incl. the recomputation of the conditioner; tfold / tcolsum / "
+                               "tstats_x / tbwd3f are reductions (latency-bound, no matrix work)" % ksteps)
+        except Exception as e:       # noqa: BLE001
+            kernels = {"error": repr(e)}
     info = {"ms_per_step": elapsed / steps * 1e3, "value": batch * world * N / (elapsed / steps) if same else None, "unit": "points/s",
             "n_gpus": world, "steps": steps, "warmup": warmup, "layers": layers, "clouds_per_gpu": batch, "points_per_cloud": N,
             "latent": G, "loss": float(loss.detach()), "precision": _train_precision(),
@@ -1140,7 +1191,8 @@ def train_step_leg(args, rank, world, dist, device, batch, layers, steps, warmup
 
 def leg_train(args, rank, world, dist, device):
     batch, global_clouds = clouds_of_rank(args, rank, world)
-    info = train_step_leg(args, rank, world, dist, device, batch, args.layers, args.steps, args.warmup)
+    info = train_step_leg(args, rank, world, dist, device, batch, args.layers, args.steps, args.warmup,
+                          dump_dir=getattr(args, "dump_outputs", None) if rank == 0 else None)
     if rank != 0:
         return None, {}
     cfg = CONFIGS[args.config]
@@ -1181,6 +1233,7 @@ def extra_config_legs(args, rank, world, device):
             a2.config, a2.batch, a2.points, a2.latent = over["config"], None, cfg["points"], cfg["latent"]
             a2.layers = over.get("layers", 14)
             a2.no_extra, a2.no_cpu_baseline, a2.pipelined, a2.streams = True, True, 0, 1
+            a2.dump_outputs = None
             if over["config"] == "cfg5":
                 a2.steps, a2.warmup, a2.settle = 4, 2, 0
                 line, _ = leg_cfg5(a2, rank, world, None, device)
@@ -1218,6 +1271,7 @@ def per_rank_proxy(args, device):
             a2 = copy.copy(args)
             a2.batch, a2.strong = bl, False
             a2.no_extra, a2.no_cpu_baseline, a2.pipelined, a2.streams = True, True, 0, 1
+            a2.dump_outputs = None
             a2.steps, a2.warmup, a2.settle = 400, 100, 200
             line, _ = leg_eval(a2, 0, 1, None, device)
             t = line["ms_per_step"] * 1e-3
@@ -1312,13 +1366,13 @@ def main(argv=None):
         line, extra = leg_eval(args, rank, world, dist, device)
         if rank == 0:
             Watchdog.keep(dict(line, extra=dict(extra)))      # (a stall in one of the extras below prints this, see Watchdog._watch)
-        if not args.no_extra and args.config == "cfg2" and args.layers == 14 and not args.no_configs:
+        if args.full and not args.no_extra and args.config == "cfg2" and args.layers == 14 and not args.no_configs:
             try:
                 Watchdog.beat("extra: the other configs")
                 extra["configs"] = extra_config_legs(args, rank, world, device)
             except Exception as e:       # noqa: BLE001
                 extra["configs_error"] = repr(e)
-        if not args.no_extra:
+        if args.full and not args.no_extra:
             # the training step with its single gradient all-reduce, on the default run too: at N > 1 this is where RCCL carries
             # the 40 / 52 MB flat gradient over xGMI (every rank takes part; reported by rank 0)
             try:
@@ -1327,7 +1381,7 @@ def main(argv=None):
                 extra["train_step"] = train_step_leg(args, rank, world, dist, device, batch, 63, args.train_steps, 16)
             except Exception as e:       # noqa: BLE001 -- never lose the headline line to an extra
                 extra["train_step_error"] = repr(e)
-        if not args.no_extra and not args.no_proxy and world == 1 and args.config == "cfg2" and args.layers == 14 and args.batch is None:
+        if args.full and not args.no_extra and not args.no_proxy and world == 1 and args.config == "cfg2" and args.layers == 14 and args.batch is None:
             try:                                         # rank-local, no collective: the single-GPU run only
                 Watchdog.beat("extra: per-rank proxies")
                 extra["per_rank_proxy"] = per_rank_proxy(args, device)

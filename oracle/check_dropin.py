@@ -33,6 +33,7 @@ sys.path.insert(0, ROOT)
 
 from oracle import flow_oracle as FO          # noqa: E402
 from oracle import model_oracle as MO         # noqa: E402
+from oracle import golden_io                  # noqa: E402
 
 
 def _load(pkg, name, path):
@@ -333,7 +334,7 @@ def svr_sections(ref_models, ref_losses, mir_models, mir_losses, em, write):
 
 def write_or_check(gold, path, write, what):
     if write:
-        np.savez_compressed(path, **gold)
+        golden_io.save(path, gold)
         print("wrote %s (%d arrays, %.0f KB)" % (path, len(gold), os.path.getsize(path) / 1024))
     else:
         old = np.load(path)

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import detrng
+from . import golden_io
 from . import flow_oracle as FO
 from . import encoder_oracle as EO
 from . import gprior_oracle as GO
@@ -97,7 +98,10 @@ def gen_layer(flows):
                         if k.endswith("running_mean") or k.endswith("running_var"):
                             out[tag + "/stats/" + k] = v.numpy()
                 meta["cases"].append({"tag": tag, "warp": list(warp), "mode": mode, "bn": bn, "seed": seed})
-    np.savez_compressed(os.path.join(OUT, "flow_layer.npz"), **out)
+    for part in golden_io.PARTS["flow_layer"]:         # split by case: each file under 1 MiB
+        pairs = part.endswith("_pairs")
+        golden_io.save(os.path.join(OUT, part + ".npz"),
+                       {k: v for k, v in out.items() if (len(k.split("_")[0]) > 2) == pairs})
     with open(os.path.join(OUT, "flow_layer.json"), "w") as f:
         json.dump(meta, f, indent=1)
 

@@ -12,6 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 
 from oracle import flow_oracle as FO            # noqa: E402
+from oracle import golden_io                    # noqa: E402
 from oracle import structural as S              # noqa: E402
 from oracle.gen_golden import layer_inputs, chamfer_inputs   # noqa: E402
 from dpf_nets_amd.networks import CondRealNVPFlow3D, LocalCondRNVPDecoder   # noqa: E402
@@ -39,7 +40,7 @@ def timeit(fn, n=20):
 
 def main():
     print(torch.cuda.get_device_name(0))
-    gold = np.load(os.path.join(ROOT, "tests/golden/flow_layer.npz"))
+    gold = golden_io.load(os.path.join(ROOT, "tests", "golden"), "flow_layer")
     meta = json.load(open(os.path.join(ROOT, "tests/golden/flow_layer.json")))
     B, N, F, G = meta["B"], meta["N"], meta["F"], meta["G"]
     for prec in ("bf16x6", "bf16x3", "bf16"):

@@ -83,3 +83,36 @@ def test_a_stall_behind_the_measured_line_does_not_lose_it():
     assert len(lines) == 1 and lines[0]["selftest"] and lines[0]["n_gpus"] == 1
     wd = lines[0]["extra"]["watchdog"]
     assert wd["rank"] == 0 and "behind the measured line" in wd["last_stage"] and "stalled" in lines[0]["extra"]["note"]
+
+
+def test_plain_run_is_lean_and_full_is_opt_in():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    """float32 stays float32, integer indices become exact float64, and an array over its share of the 64 MB budget is
+    written as the same seeded sample every time."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    pts = torch.randn(2, 3, 5)
+    idx = torch.tensor([[0, 7, 2**24 + 1]], dtype=torch.int32)
+    big = torch.arange(bench.DUMP_BUDGET_BYTES // 8 + 100, dtype=torch.float64)      # element i holds i: positions stay readable
+    arrays = {"points": pts, "idx": idx, "big": big}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    p = np.load(tmp_path / "a" / "points.npy")
+    assert p.dtype == np.float32 and np.array_equal(p, pts.numpy())
+    i = np.load(tmp_path / "a" / "idx.npy")
+    assert i.dtype == np.float64 and np.array_equal(i, idx.numpy().astype(np.float64))
+    total = sum(os.path.getsize(tmp_path / "a" / (n + ".npy")) for n in arrays)
+    assert total <= bench.DUMP_BUDGET_BYTES + 3 * 128
+    s1, s2 = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert s1.dtype == np.float64 and s1.size < big.numel() and np.array_equal(s1, s2)
+    assert np.all(np.diff(s1) > 0) and s1[0] >= 0 and s1[-1] < big.numel()

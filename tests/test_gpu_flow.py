@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from oracle import flow_oracle as FO
+from oracle import golden_io
 from oracle.gen_golden import layer_inputs
 
 pytestmark = pytest.mark.gpu
@@ -59,7 +60,7 @@ def tiling(request):
 
 
 def _load(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name + ".npz")), json.load(open(os.path.join(golden_dir, name + ".json")))
+    return golden_io.load(golden_dir, name), json.load(open(os.path.join(golden_dir, name + ".json")))
 
 
 @pytest.mark.parametrize("prec", ["f16x3", "bf16x3", "bf16x6", "bf16"])

@@ -24,6 +24,7 @@ import pytest
 import torch
 
 from oracle import flow_oracle as FO
+from oracle import golden_io
 from oracle.gen_golden import layer_inputs, _grad_projection
 
 pytestmark = pytest.mark.gpu
@@ -96,7 +97,7 @@ def close_but_kinks(got, ref, tol, what, KINK_FRACTION=2e-4):
 
 
 def _load(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name + ".npz")), json.load(open(os.path.join(golden_dir, name + ".json")))
+    return golden_io.load(golden_dir, name), json.load(open(os.path.join(golden_dir, name + ".json")))
 
 
 def _check_gproj(named_grads, gold, prefix, seed, tol=1e-3):

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from oracle import flow_oracle as FO
+from oracle import golden_io
 from oracle.gen_golden import layer_inputs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -69,7 +70,7 @@ def test_state_dict_contract(golden_dir):
 def test_training_path_matches_reference_golden(golden_dir):
     """The tensor-op (training-mode BN) path of the mirror module == the reference module."""
     from dpf_nets_amd.networks import CondRealNVPFlow3D
-    gold = np.load(os.path.join(golden_dir, "flow_layer.npz"))
+    gold = golden_io.load(golden_dir, "flow_layer")
     meta = json.load(open(os.path.join(golden_dir, "flow_layer.json")))
     B, N, F, G = meta["B"], meta["N"], meta["F"], meta["G"]
     for case in meta["cases"]:

@@ -10,6 +10,7 @@ import torch
 
 from oracle import detrng
 from oracle import flow_oracle as FO
+from oracle import golden_io
 from oracle import structural as S
 from oracle.gen_golden import layer_inputs, chamfer_inputs, _grad_projection
 
@@ -17,7 +18,7 @@ RTOL, ATOL = 1e-5, 2e-6   # oracle and reference are both fp32 torch-CPU; only o
 
 
 def _load(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name + ".npz")), json.load(open(os.path.join(golden_dir, name + ".json")))
+    return golden_io.load(golden_dir, name), json.load(open(os.path.join(golden_dir, name + ".json")))
 
 
 def test_param_spec_matches_reference_state_dict(golden_dir):

@@ -17,7 +17,7 @@ CONFIGS = [
     ("cfg-5 whole B=16 N=8192 L=63 on one GPU", ["--batch", "16", "--points", "8192", "--layers", "63"]),
 ]
 for name, extra in CONFIGS:
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--steps", "50",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--steps", "50",
                           "--warmup", "10"] + extra, capture_output=True, text=True)
     try:
         d = json.loads(out.stdout.strip().splitlines()[-1])

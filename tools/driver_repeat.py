@@ -1,4 +1,4 @@
-"""The driver's exact command, R times in fresh processes on THIS box: min / median / max of the line's ms_per_step and of the flat
+"""The driver's command plus --full (the per-kernel figures and the training step), R times in fresh processes on THIS box: min / median / max of the line's ms_per_step and of the flat
 scalars that tell a slow box from a regression from a gap in the window.
     python tools/driver_repeat.py [R] [out.json]"""
 import json, os, subprocess, sys
@@ -7,7 +7,7 @@ root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 rows = []
 for i in range(R):
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"], capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"], capture_output=True, text=True)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if r.returncode != 0 or not line:
         rows.append({"rc": r.returncode, "stderr": r.stderr[-400:]})
@@ -21,7 +21,7 @@ ok = [r for r in rows if "us_per_step" in r]
 def mmm(k):
     v = np.array([r[k] for r in ok if r.get(k) is not None], float)
     return {"min": float(v.min()), "median": float(np.median(v)), "max": float(v.max())} if len(v) else None
-out = {"command": "python3 bench.py --gpus 1 --steps 20 --warmup 5", "runs": R, "ok": len(ok),
+out = {"command": "python3 bench.py --gpus 1 --steps 20 --warmup 5 --full", "runs": R, "ok": len(ok),
        "summary": {k: mmm(k) for k in ("us_per_step", "us_per_step_wall", "kernels_sum_us", "flow_us", "nn_us", "film_us", "sclk_mhz", "train_ms")},
        "rows": rows}
 s = json.dumps(out, indent=1)

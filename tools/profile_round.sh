@@ -17,12 +17,12 @@ cd $GRAFT_REPO_ROOT
 bash tools/pmc_run.sh ${TAG}_prof/pmc > /dev/null 2>&1
 cp profiles/traffic.json $OUT/traffic.json 2>/dev/null
 python3 tools/pmc_traffic.py $OUT/pmc B32_N2048_L14_f16x3 $OUT/traffic.json "profiles/${TAG}_pmc_pass4.txt + ${TAG}_pmc_pass5.txt" > /dev/null 2>&1
-python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-python3 bench.py --layers 63 --no-extra --no-cpu-baseline > $OUT/bench_L63.json 2>> $OUT/bench_default.err
-python3 bench.py --layers 15 --no-extra --no-cpu-baseline > $OUT/bench_L15.json 2>> $OUT/bench_default.err
-python3 bench.py --config cfg3 --no-extra > $OUT/bench_cfg3.json 2>> $OUT/bench_default.err
-python3 bench.py --config cfg5 > $OUT/bench_cfg5.json 2>> $OUT/bench_default.err
-python3 bench.py --no-graph --no-extra --no-cpu-baseline > $OUT/bench_eager.json 2>> $OUT/bench_default.err
+python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+python3 bench.py --full --layers 63 --no-extra --no-cpu-baseline > $OUT/bench_L63.json 2>> $OUT/bench_default.err
+python3 bench.py --full --layers 15 --no-extra --no-cpu-baseline > $OUT/bench_L15.json 2>> $OUT/bench_default.err
+python3 bench.py --full --config cfg3 --no-extra > $OUT/bench_cfg3.json 2>> $OUT/bench_default.err
+python3 bench.py --full --config cfg5 > $OUT/bench_cfg5.json 2>> $OUT/bench_default.err
+python3 bench.py --full --no-graph --no-extra --no-cpu-baseline > $OUT/bench_eager.json 2>> $OUT/bench_default.err
 bash tools/train_prof.sh ${TAG}_prof/train > /dev/null 2>&1
 bash tools/pmc_train.sh ${TAG}_prof/pmc_train > /dev/null 2>&1
 ls -la $OUT $OUT/train
@@ -36,7 +36,7 @@ bash tools/kt_run.sh ${TAG}_prof/emd_kernel_trace --config cfg5 --no-cpu-baselin
 bash tools/pmc_cfg5.sh ${TAG}_prof/pmc_cfg5 > /dev/null 2>&1
 python3 tools/pmc_traffic_emd.py $OUT/pmc_cfg5 16 8192 $OUT/traffic.json "profiles/${TAG}_pmc_cfg5_pass1.txt + _pass2.txt" > /dev/null 2>&1
 # r05: the rank-sized training step (B = 8, G = 512) and the phase stamps of the training kernels
-python3 bench.py --leg train --batch 8 --latent 512 --steps 40 --warmup 12 > $OUT/bench_train_B8_G512.json 2>> $OUT/bench_default.err
+python3 bench.py --full --leg train --batch 8 --latent 512 --steps 40 --warmup 12 > $OUT/bench_train_B8_G512.json 2>> $OUT/bench_default.err
 (cd dpf_nets_amd/csrc && make -s prof > /dev/null 2>&1)
 python3 tools/train_kprof.py > $OUT/train_kprof.txt 2>&1
 python3 tools/train_phase_prof.py > $OUT/train_phase_prof.txt 2>&1
