@@ -26,6 +26,8 @@ SIGNATURES = {
     "dpf_nndistance_cd": (_i, [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
     "dpf_pairwise_cd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "dpf_pairwise_cd": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dpf_pairwise_emd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "dpf_pairwise_emd": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dpf_nndistancegrad": (_i, [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dpf_approxmatch": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dpf_approxmatch_workspace_bytes": (_sz, [_i, _i, _i]),

@@ -205,23 +205,35 @@ constexpr int PPW = 128;   // points per wave in the deferred kernels
 // `gate`: the deferred path comes in two families -- these packed-VALU kernels (difference-form d^2, bit-identical to the
 // read-modify-write path) and the matrix-core passes further down (expanded-form d^2).  Which one runs is decided ON THE DEVICE
 // (emd_mfma_prep_kernel looks at the coordinates' range), so both families are launched and every kernel of the family that is
-// not wanted returns at once: gate == nullptr -> always run, else run iff *gate == want.
-__device__ __forceinline__ bool gate_closed(const unsigned *gate, unsigned want) {
-    return gate != nullptr && __builtin_nontemporal_load(gate) != want;
+// not wanted returns at once: gate == nullptr -> always run, else run iff pair bi's verdict gate[bi * gs] == want.
+// PairMap: which clouds the launch's pair bi (blockIdx.y of the per-pair kernels) reads -- cloud 1 = bi / d1 of xyz1, cloud 2 =
+// bi % d2 of xyz2 -- and the stride gs of the verdicts.  The batched entries pass {1, b, 0}: cloud bi against cloud bi, one
+// verdict for the whole call.  dpf_pairwise_emd passes {n2, n2, 1}: pair i n2 + j is (clouds1[i], clouds2[j]) with a verdict of
+// its own.  Everything else a pair owns (temp, the workspace's regions) is indexed by bi.
+struct PairMap { int d1, d2, gs; };
+__device__ __forceinline__ size_t cloud1_of(PairMap pm, int bi) { return (size_t)(bi / pm.d1); }
+__device__ __forceinline__ size_t cloud2_of(PairMap pm, int bi) { return (size_t)(bi % pm.d2); }
+// (gs is read in front of the pointer's null test -- readfirstlane is convergent, the compiler does not sink it into the branch:
+// loaded behind the test, it cost every workgroup a second dependent kernel-argument round trip, measured at cfg5 as +0.2 us
+// per gated-off launch and +0.3-0.5 us per pass-2 launch)
+__device__ __forceinline__ bool gate_closed(const unsigned *gate, PairMap pm, int bi, unsigned want) {
+    const int gs = __builtin_amdgcn_readfirstlane(pm.gs);
+    return gate != nullptr && __builtin_nontemporal_load(gate + (size_t)bi * gs) != want;
 }
 
 __global__ void emd_pack_init_kernel(int m, float multiR, const float *__restrict__ xyz2, float4 *__restrict__ c2a, size_t pstride,
-                                     const unsigned *gate) {
-    if (gate_closed(gate, 1u)) return;
+                                     const unsigned *gate, PairMap pm) {
+    if (gate_closed(gate, pm, blockIdx.y, 1u)) return;
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= m) return;
-    const float *q = xyz2 + ((size_t)blockIdx.y * m + j) * 3;
+    const float *q = xyz2 + (cloud2_of(pm, blockIdx.y) * m + j) * 3;
     c2a[(size_t)blockIdx.y * pstride + j] = make_float4(q[0], q[1], q[2], multiR);
 }
 
 // remainL = multiL, remainR = multiR                       approxmatch.cu:6-12,18-21
-__global__ void emd_init_kernel(int n, int m, float multiL, float multiR, float *__restrict__ temp, unsigned *flag) {
-    if (flag != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *flag = 0u;
+// (and the family verdicts cleared: the call's one, or every pair's)
+__global__ void emd_init_kernel(int n, int m, float multiL, float multiR, float *__restrict__ temp, unsigned *flag, PairMap pm) {
+    if (flag != nullptr && blockIdx.x == 0 && (blockIdx.y == 0 || pm.gs != 0) && threadIdx.x == 0) flag[(size_t)blockIdx.y * pm.gs] = 0u;
     float *t = temp + (size_t)blockIdx.y * (n + m) * 2;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n + m; i += gridDim.x * blockDim.x)
         t[i] = i < n ? multiL : multiR;
@@ -327,15 +339,16 @@ struct Levels { float lvl2[NLEVEL]; };
 template <int PASS>
 __global__ __launch_bounds__(1024) void emd_ratio2_kernel(int n, int m, float lvl2, const float *__restrict__ xyz1,
                                                           const float *__restrict__ xyz2, float *temp, float *rbase,
-                                                          size_t rstride, float4 *pk, size_t pstride, const unsigned *gate) {
+                                                          size_t rstride, float4 *pk, size_t pstride, const unsigned *gate,
+                                                          PairMap pm) {
     __shared__ float part[MAXS][PPW];
-    if (gate_closed(gate, 1u)) return;
     const int bi = blockIdx.y;
+    if (gate_closed(gate, pm, bi, 1u)) return;
     const int lane = threadIdx.x, slice = __builtin_amdgcn_readfirstlane(threadIdx.y), S = blockDim.y;
     float *t = temp + (size_t)bi * (n + m) * 2;
     float *remainL = t, *remainR = t + n, *ratioL = rbase + (size_t)bi * rstride, *ratioR = ratioL + n;
     const int np = PASS == 1 ? n : m, nq = PASS == 1 ? m : n;
-    const float *__restrict__ P = (PASS == 1 ? xyz1 + (size_t)bi * n * 3 : xyz2 + (size_t)bi * m * 3);
+    const float *__restrict__ P = (PASS == 1 ? xyz1 + cloud1_of(pm, bi) * n * 3 : xyz2 + cloud2_of(pm, bi) * m * 3);
     float4 *c1 = pk + (size_t)bi * pstride, *c2a = c1 + n, *c2b = c2a + m;
     const int i0 = blockIdx.x * PPW + lane, i1 = i0 + 64;
     const int a0 = min(i0, np - 1), a1 = min(i1, np - 1);
@@ -377,14 +390,14 @@ __global__ __launch_bounds__(1024) void emd_ratio2_kernel(int n, int m, float lv
 
 __global__ __launch_bounds__(1024) void emd_match2_kernel(int n, int m, float lvl2, const float *__restrict__ xyz1,
                                                           float *temp, const float *rbase, size_t rstride,
-                                                          const float4 *pk, size_t pstride, const unsigned *gate) {
+                                                          const float4 *pk, size_t pstride, const unsigned *gate, PairMap pm) {
     __shared__ float part[MAXS][PPW];
-    if (gate_closed(gate, 1u)) return;
     const int bi = blockIdx.y;
+    if (gate_closed(gate, pm, bi, 1u)) return;
     const int lane = threadIdx.x, slice = __builtin_amdgcn_readfirstlane(threadIdx.y), S = blockDim.y;
     float *remainL = temp + (size_t)bi * (n + m) * 2;
     const float *__restrict__ ratioL = rbase + (size_t)bi * rstride;
-    const float *__restrict__ P = xyz1 + (size_t)bi * n * 3;
+    const float *__restrict__ P = xyz1 + cloud1_of(pm, bi) * n * 3;
     const int k0 = blockIdx.x * PPW + lane, k1 = k0 + 64;
     const int a0 = min(k0, n - 1), a1 = min(k1, n - 1);
     const f2 px = {P[a0 * 3 + 0], P[a1 * 3 + 0]}, py = {P[a0 * 3 + 1], P[a1 * 3 + 1]}, pz = {P[a0 * 3 + 2], P[a1 * 3 + 2]};
@@ -463,10 +476,10 @@ __device__ __forceinline__ int round_up(int v, int q) { return (v + q - 1) / q *
 // One workgroup per cloud: cloud 1's centroid (fixed-order sums), the grid exponent g from the largest centred, scaled
 // coordinate of either cloud, and whether every point of both clouds is in range
 __global__ __launch_bounds__(1024) void emd_mfma_prep_kernel(int n, int m, const float *__restrict__ xyz1, const float *__restrict__ xyz2,
-                                                             float *__restrict__ meta, unsigned *flag) {
+                                                             float *__restrict__ meta, unsigned *flag, PairMap pm) {
     __shared__ float red[3][1024];
     const int bi = blockIdx.x, tid = threadIdx.x;
-    const float *p1 = xyz1 + (size_t)bi * n * 3, *p2 = xyz2 + (size_t)bi * m * 3;
+    const float *p1 = xyz1 + cloud1_of(pm, bi) * n * 3, *p2 = xyz2 + cloud2_of(pm, bi) * m * 3;
     float sx = 0.f, sy = 0.f, sz = 0.f;
     for (int i = tid; i < n; i += 1024) { sx += p1[i * 3 + 0]; sy += p1[i * 3 + 1]; sz += p1[i * 3 + 2]; }
     red[0][tid] = sx; red[1][tid] = sy; red[2][tid] = sz;
@@ -501,7 +514,7 @@ __global__ __launch_bounds__(1024) void emd_mfma_prep_kernel(int n, int m, const
         float *mt = meta + (size_t)bi * METAF;
         mt[0] = cx; mt[1] = cy; mt[2] = cz; mt[3] = (float)bad; mt[4] = ldexpf(1.f, g); mt[5] = (float)(14 - 2 * g);
         mt[6] = 0.f; mt[7] = 0.f;
-        if (bad) atomicOr(flag, 1u);
+        if (bad) atomicOr(flag + (size_t)bi * pm.gs, 1u);
     }
 }
 
@@ -532,6 +545,7 @@ struct MfmaState {
     float *temp;            // reference layout: remainL (n) | remainR (m) | ...
     size_t rstride;         // per-cloud stride of a level's ratio slot [ratioL (n) | ratioR (m)]
     const unsigned *gate;
+    PairMap pm;             // the pairs' clouds and verdicts (gate_closed)
 };
 
 // fp16 operand records of a point (header of this section).  In grid units q' = a + alpha (rows: cloud 2, the A operand),
@@ -606,13 +620,14 @@ __device__ __forceinline__ void level_vectors(LevelFac lf, int half, bool rows, 
 // zeros in every level's ratioR slot of the workspace (a point that has left the auction is not written again)
 __global__ void emd_mfma_pack_kernel(MfmaState st, float multiR, const float *__restrict__ xyz1, const float *__restrict__ xyz2,
                                      const float *__restrict__ meta, u4 *__restrict__ recA2_dense, float *__restrict__ ws, size_t lstride) {
-    if (gate_closed(st.gate, 0u)) return;
     const int idx = blockIdx.x * blockDim.x + threadIdx.x, bi = blockIdx.y;
+    if (gate_closed(st.gate, st.pm, bi, 0u)) return;
     if (idx >= st.NP + st.MP) return;
     const bool first = idx < st.NP;
     const int k = first ? idx : idx - st.NP;
     const bool live = k < (first ? st.n : st.m);
-    const float *q = first ? xyz1 + ((size_t)bi * st.n + (live ? k : 0)) * 3 : xyz2 + ((size_t)bi * st.m + (live ? k : 0)) * 3;
+    const float *q = first ? xyz1 + (cloud1_of(st.pm, bi) * st.n + (live ? k : 0)) * 3
+                           : xyz2 + (cloud2_of(st.pm, bi) * st.m + (live ? k : 0)) * 3;
     u4 ra[RECQ], rb[RECQ];
     point_records(q, meta + (size_t)bi * METAF, live, ra, rb);
     if (first) {
@@ -759,7 +774,7 @@ __device__ __forceinline__ void loads_stay_behind(float (&v)[N]) {
 template <int MODE>
 __global__ __launch_bounds__(64 * MSL) void emd_mfma_cols_kernel(MfmaState st, int cur, LevelFac lf, float *rb_cur) {
     __shared__ float part[MSL][MPW];
-    if (gate_closed(st.gate, 0u)) return;
+    if (gate_closed(st.gate, st.pm, blockIdx.y, 0u)) return;
     const f16acc zacc = opaque_zero();
     const int bi = blockIdx.y, lane = threadIdx.x, slice = __builtin_amdgcn_readfirstlane(threadIdx.y), S = blockDim.y;
     const int half = lane >> 5, col = lane & 31;
@@ -867,7 +882,7 @@ template <int RT>
 __global__ __launch_bounds__(64 * MSL) void emd_mfma_rows_kernel(MfmaState st, int cur, LevelFac lf, float *rb_cur, int regime) {
     constexpr int RPW = 32 * RT;                                    // rows per workgroup
     __shared__ float part[MSL][RPW];
-    if (gate_closed(st.gate, 0u)) return;
+    if (gate_closed(st.gate, st.pm, blockIdx.y, 0u)) return;
     const f16acc zacc = opaque_zero();
     const int bi = blockIdx.y, lane = threadIdx.x, slice = __builtin_amdgcn_readfirstlane(threadIdx.y), S = blockDim.y;
     const int cnt = st.count[bi];
@@ -976,7 +991,7 @@ template <bool LAST>
 __global__ __launch_bounds__(1024) void emd_mfma_compact_kernel(MfmaState st, int cur, int q) {
     __shared__ int wsum[2][16];
     __shared__ int total;
-    if (gate_closed(st.gate, 0u)) return;
+    if (gate_closed(st.gate, st.pm, blockIdx.x, 0u)) return;
     const int bi = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nxt = cur ^ 1;
     const int cnt = st.count[bi];
     const size_t base = (size_t)bi * st.MP;
@@ -1038,8 +1053,8 @@ __global__ __launch_bounds__(1024) void emd_mfma_compact_kernel(MfmaState st, in
 __global__ void emd_mfma_gather_kernel(MfmaState st, const u4 *__restrict__ recA2_dense, const float *__restrict__ xyz2,
                                        const float *__restrict__ ws, size_t lstride, u4 *__restrict__ recA_s,
                                        float *__restrict__ rr_s, float *__restrict__ c2soa_s, int *__restrict__ l_s) {
-    if (gate_closed(st.gate, 0u)) return;
     const int pos = blockIdx.x * blockDim.x + threadIdx.x, bi = blockIdx.y;
+    if (gate_closed(st.gate, st.pm, bi, 0u)) return;
     if (pos >= st.MP) return;
     const bool valid = pos < st.m;
     const size_t at = (size_t)bi * st.MP + pos;
@@ -1049,7 +1064,7 @@ __global__ void emd_mfma_gather_kernel(MfmaState st, const u4 *__restrict__ recA
     for (int u = 0; u < RECQ; ++u) recA_s[at * RECQ + u] = valid ? recA2_dense[((size_t)bi * st.MP + l) * RECQ + u] : z;
     for (int qv = 0; qv < NLEVEL; ++qv)
         rr_s[((size_t)qv * st.nb + bi) * st.MP + pos] = valid ? ws[qv * lstride + (size_t)bi * st.rstride + st.n + l] : 0.f;
-    const float *p = xyz2 + ((size_t)bi * st.m + l) * 3;
+    const float *p = xyz2 + (cloud2_of(st.pm, bi) * st.m + l) * 3;
     for (int u = 0; u < 3; ++u) c2soa_s[((size_t)bi * 3 + u) * st.MP + pos] = valid ? p[u] : 0.f;
     l_s[at] = valid ? l : -1;
 }
@@ -1063,7 +1078,9 @@ struct LevelScales { LevelFac lf[NLEVEL]; };
 // all zero there) -- per (pair, live level): exp2, a multiplication, an FMA.  The accumulator layout writes 128 contiguous
 // bytes of a `match` row per register and half-wave.
 // COST: sum match * |x1 - x2| with the distance in the difference form, partial sums per (cloud, workgroup, slice) for
-// emd_cost_sum_kernel -- fixed order, deterministic.
+// emd_cost_sum_kernel -- fixed order, deterministic; cstride floats per pair (approxmatch_impl: the same for both families).
+// STORE = false (dpf_pairwise_emd): the same sums, `match` not written -- the only difference is the store; the skip below
+// and every operation of the sum are those of the storing variant.
 // Measured (cfg5, 16 x 8192^2): 1.18 ms = `match` written at 3.6 TB/s; MTM = 4 (512 contiguous bytes per row and wave) and the
 // unmasked store path moved it by < 10 %: it is the write that bounds it, not the instruction count.
 constexpr int MTM = 2;
@@ -1077,7 +1094,7 @@ constexpr int MTM = 2;
 #else
 #define EMD_MATCH_STORE(v, p) (*(p) = (v))
 #endif
-template <bool COST>
+template <bool COST, bool STORE>
 // (no __restrict__ on what the loop loads: a load from memory the compiler knows nobody writes may cross the asm barriers that
 // keep loads and MFMAs apart -- loads_stay_behind / mfmas_stay_behind -- and r06's first build sank the last ratioR load of a
 // level behind that level's MFMAs, into the registers of a fragment they read)
@@ -1085,18 +1102,18 @@ __global__ __launch_bounds__(64 * MSL) void emd_mfma_materialize_kernel(MfmaStat
                                                                         const float *ws, size_t lstride,
                                                                         const u4 *recA_s, const float *rr_s,
                                                                         const float *c2soa_s, const int *l_s,
-                                                                        float *match, float *costpart) {
+                                                                        float *match, float *costpart, int cstride) {
     __shared__ float rl_s[MSL][NLEVEL][32 * MTM];     // ratioL of the wave's columns, by level (a register array would be indexed
     __shared__ u4 sv_s[NLEVEL][2][2][2];              //   dynamically by the level loop -- scratch -- or unrolled nine times -- spills)
                                                       // sv_s[level][rows | columns][half][MFMA]: level_vectors
     __shared__ int cnt_s[NLEVEL];
-    if (gate_closed(st.gate, 0u)) return;
+    if (gate_closed(st.gate, st.pm, blockIdx.y, 0u)) return;
     const f16acc zacc = opaque_zero();
     const int bi = blockIdx.y, nb = gridDim.y, lane = threadIdx.x, slice = __builtin_amdgcn_readfirstlane(threadIdx.y), S = blockDim.y;
     const int half = lane >> 5, col = lane & 31;
     const u4 *ownrec = st.recB1 + ((size_t)bi * st.NP + blockIdx.x * (32 * MTM)) * RECQ;
     const u4 *candrec = recA_s + ((size_t)bi * st.MP + col) * RECQ + half;
-    float *mt = match + (size_t)bi * st.n * st.m;
+    float *mt = STORE ? match + (size_t)bi * st.n * st.m : nullptr;
     u4 bfraw[MTM][2];
     float px[MTM], py[MTM], pz[MTM];
     int kk[MTM];
@@ -1117,7 +1134,7 @@ __global__ __launch_bounds__(64 * MSL) void emd_mfma_materialize_kernel(MfmaStat
 #pragma unroll
             for (int j = 0; j < NLEVEL; ++j) rl_s[slice][j][t * 32 + col] = ws[j * lstride + (size_t)bi * st.rstride + kc];
         if (COST) {
-            const float *p = xyz1 + ((size_t)bi * st.n + kc) * 3;
+            const float *p = xyz1 + (cloud1_of(st.pm, bi) * st.n + kc) * 3;
             px[t] = p[0]; py[t] = p[1]; pz[t] = p[2];
         }
     }
@@ -1176,7 +1193,7 @@ __global__ __launch_bounds__(64 * MSL) void emd_mfma_materialize_kernel(MfmaStat
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) {
                     const int l = jj == 0 ? l4.x : jj == 1 ? l4.y : jj == 2 ? l4.z : l4.w;
-                    float *row = mt + (size_t)(FULL ? l : max(l, 0)) * st.n + kk[0];
+                    float *row = STORE ? mt + (size_t)(FULL ? l : max(l, 0)) * st.n + kk[0] : nullptr;
                     const float cx = jj == 0 ? qx.x : jj == 1 ? qx.y : jj == 2 ? qx.z : qx.w;
                     const float cy = jj == 0 ? qy.x : jj == 1 ? qy.y : jj == 2 ? qy.z : qy.w;
                     const float cz = jj == 0 ? qz.x : jj == 1 ? qz.y : jj == 2 ? qz.z : qz.w;
@@ -1184,7 +1201,7 @@ __global__ __launch_bounds__(64 * MSL) void emd_mfma_materialize_kernel(MfmaStat
                     for (int t = 0; t < MTM; ++t) {
                         const float v = mm[t][4 * i + jj];
                         const bool live = FULL || (l >= 0 && kk[t] < st.n);
-                        if (live) EMD_MATCH_STORE(v, &row[32 * t]);
+                        if (STORE && live) EMD_MATCH_STORE(v, &row[32 * t]);
                         // the distance only where some entry of the wave's 2 x 32 is worth it: almost every pair's weight is below
                         // 1e-12 of a matched pair's (what is skipped sums to < 1e-6 of the cost)
                         if (COST && __ballot(live && v > 1e-12f) != 0ull) {
@@ -1200,7 +1217,7 @@ __global__ __launch_bounds__(64 * MSL) void emd_mfma_materialize_kernel(MfmaStat
     }
     if (COST) {
         for (int o = 32; o > 0; o >>= 1) cost += __shfl_xor(cost, o);
-        if (lane == 0) costpart[((size_t)bi * gridDim.x + blockIdx.x) * S + slice] = cost;
+        if (lane == 0) costpart[(size_t)bi * cstride + blockIdx.x * S + slice] = cost;
     }
 }
 
@@ -1208,7 +1225,7 @@ __global__ __launch_bounds__(64 * MSL) void emd_mfma_materialize_kernel(MfmaStat
 // same level vectors, same two MFMAs): out[l * n + k], l a point of cloud 2, k of cloud 1.  One 32 x 32 tile per wave.
 __global__ __launch_bounds__(64) void emd_mfma_debug_exponents_kernel(MfmaState st, LevelFac lf, const u4 *__restrict__ recA2_dense,
                                                                       float *__restrict__ out, unsigned slot_mask) {
-    if (gate_closed(st.gate, 0u)) return;
+    if (gate_closed(st.gate, st.pm, 0, 0u)) return;
     const f16acc zacc = opaque_zero();
     const int lane = threadIdx.x, half = lane >> 5, col = lane & 31;
     u4 svr[2], svc[2];
@@ -1243,12 +1260,12 @@ bool g_matrix_path = true;
 
 // (xyz2_l, ratioR_level0..8[l]) records of 12 floats for the materialisation
 __global__ void emd_pack_levels_kernel(int n, int m, const float *__restrict__ xyz2, const float *__restrict__ ws,
-                                       size_t lstride, size_t rstride, float *__restrict__ rec, const unsigned *gate) {
-    if (gate_closed(gate, 1u)) return;
+                                       size_t lstride, size_t rstride, float *__restrict__ rec, const unsigned *gate, PairMap pm) {
+    const int bi = blockIdx.y;
+    if (gate_closed(gate, pm, bi, 1u)) return;
     const int l = blockIdx.x * blockDim.x + threadIdx.x;
     if (l >= m) return;
-    const int bi = blockIdx.y;
-    const float *q = xyz2 + ((size_t)bi * m + l) * 3;
+    const float *q = xyz2 + (cloud2_of(pm, bi) * m + l) * 3;
     float4 *o = (float4 *)(rec + ((size_t)bi * m + l) * 12);
     float w[NLEVEL];
 #pragma unroll
@@ -1274,17 +1291,19 @@ __device__ __forceinline__ f2 level_sum(const LevelPairs &lv, const u64 *r, cons
 
 // COST: also the matching's cost sum_{l,k} match[l][k] * |x1_k - x2_l| (approxmatch.cu:184-224) of this wave's
 // pairs -- the distance is already there -- to costpart[(cloud, workgroup, slice)]; emd_cost_sum_kernel adds a cloud's
-// partials in a fixed order.  Saves matchcost's pass over `match` (4*n*m bytes per cloud).
-template <bool COST>
+// partials in a fixed order.  Saves matchcost's pass over `match` (4*n*m bytes per cloud).  STORE = false (dpf_pairwise_emd):
+// the same sums without writing `match`.
+template <bool COST, bool STORE>
 __global__ __launch_bounds__(1024) void emd_materialize2_kernel(int n, int m, LevelPairs lv, const float *__restrict__ xyz1,
                                                                 const float *__restrict__ rec, float *__restrict__ match,
                                                                 const float *__restrict__ ws, size_t lstride, size_t rstride,
-                                                                float *__restrict__ costpart, const unsigned *gate) {
-    if (gate_closed(gate, 1u)) return;
+                                                                float *__restrict__ costpart, int cstride, const unsigned *gate,
+                                                                PairMap pm) {
     const int bi = blockIdx.y;
+    if (gate_closed(gate, pm, bi, 1u)) return;
     const int lane = threadIdx.x, slice = __builtin_amdgcn_readfirstlane(threadIdx.y), S = blockDim.y;
-    const float *__restrict__ P = xyz1 + (size_t)bi * n * 3;
-    float *__restrict__ mt = match + (size_t)bi * n * m;
+    const float *__restrict__ P = xyz1 + cloud1_of(pm, bi) * n * 3;
+    float *__restrict__ mt = STORE ? match + (size_t)bi * n * m : nullptr;
     const int k0 = blockIdx.x * PPW + lane, k1 = k0 + 64;
     const int a0 = min(k0, n - 1), a1 = min(k1, n - 1);
     const f2 px = {P[a0 * 3 + 0], P[a1 * 3 + 0]}, py = {P[a0 * 3 + 1], P[a1 * 3 + 1]}, pz = {P[a0 * 3 + 2], P[a1 * 3 + 2]};
@@ -1299,24 +1318,26 @@ __global__ __launch_bounds__(1024) void emd_materialize2_kernel(int n, int m, Le
     stream_records<6, 2>((const u64 *)(rec + (size_t)bi * m * 12), lb, le, [&](int l, const u64 *r) {
         const f2 d2 = sqdist2(px, py, pz, r[0], r[1]);
         const f2 acc = level_sum<NLEVEL - 1>(lv, r, rl, d2);
-        float *row = mt + (size_t)l * n;
-        if (k0 < n) EMD_MATCH_STORE(acc.x, &row[k0]);
-        if (k1 < n) EMD_MATCH_STORE(acc.y, &row[k1]);
+        if (STORE) {
+            float *row = mt + (size_t)l * n;
+            if (k0 < n) EMD_MATCH_STORE(acc.x, &row[k0]);
+            if (k1 < n) EMD_MATCH_STORE(acc.y, &row[k1]);
+        }
         if (COST) cost = fma2(acc, f2{__builtin_amdgcn_sqrtf(d2.x), __builtin_amdgcn_sqrtf(d2.y)}, cost);
     });
     if (COST) {
         float c = (k0 < n ? cost.x : 0.f) + (k1 < n ? cost.y : 0.f);
         for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-        if (lane == 0) costpart[((size_t)bi * gridDim.x + blockIdx.x) * S + slice] = c;
+        if (lane == 0) costpart[(size_t)bi * cstride + blockIdx.x * S + slice] = c;
     }
 }
 
-// out[b] = the cloud's partial costs, added in a fixed order
-__global__ __launch_bounds__(256) void emd_cost_sum_kernel(int nper, const float *__restrict__ costpart, float *__restrict__ out,
-                                                           const unsigned *gate, unsigned want) {
+// out[b] = the cloud's nper partial costs (at cstride floats per cloud), added in a fixed order
+__global__ __launch_bounds__(256) void emd_cost_sum_kernel(int nper, int cstride, const float *__restrict__ costpart,
+                                                           float *__restrict__ out, const unsigned *gate, unsigned want, PairMap pm) {
     __shared__ float red[4];
-    if (gate != nullptr && __builtin_nontemporal_load(gate) != want) return;
-    const float *cp = costpart + (size_t)blockIdx.x * nper;
+    if (gate_closed(gate, pm, blockIdx.x, want)) return;
+    const float *cp = costpart + (size_t)blockIdx.x * cstride;
     float c = 0.f;
     for (int i = threadIdx.x; i < nper; i += 256) c += cp[i];
     for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
@@ -1570,13 +1591,22 @@ extern "C" int dpf_emd_set_matrix_path(int on) {
     return prev;
 }
 
+// A pairwise call (dpf_pairwise_emd): the b pairs' clouds and verdicts (PairMap), the verdicts' array (b words; the batched
+// entries keep their one word in the matrix-core regions), and the batch size the slice counts are picked for -- fixed by the
+// entry, not the launch's b, so that a pair's partial sums do not depend on how many pairs share its launch.  `match` may be
+// NULL: the materialisation passes then only sum the cost.
+struct PairCall { PairMap pm; unsigned *gates; int slice_b; };
+
 static int approxmatch_impl(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *temp, float *cost,
-                            void *workspace, size_t workspace_bytes, dpf_stream_t stream) {
+                            void *workspace, size_t workspace_bytes, dpf_stream_t stream, const PairCall *pc = nullptr) {
     if (b < 0 || n <= 0 || m <= 0) return DPF_EINVAL;
     if (b == 0) return 0;
-    if (!xyz1 || !xyz2 || !match || !temp) return DPF_EINVAL;
+    if (!xyz1 || !xyz2 || !temp || (!match && !pc)) return DPF_EINVAL;
     if (b > 65535) return DPF_ENOSUP;
     const bool deferred = workspace != nullptr && workspace_bytes >= dpf_approxmatch_workspace_bytes(b, n, m);
+    if (pc && (!deferred || !cost)) return DPF_EINVAL;
+    const PairMap pm = pc ? pc->pm : PairMap{1, b, 0};
+    const int sb = pc ? pc->slice_b : b;
     hipStream_t s = (hipStream_t)stream;
     float multiL, multiR;
     if (n >= m) { multiL = 1; multiR = (float)(n / m); }   // integer division, approxmatch.cu:6-12
@@ -1587,10 +1617,10 @@ static int approxmatch_impl(int b, int n, int m, const float *xyz1, const float 
     const int NP = (n + MPW - 1) / MPW * MPW, MP = (m + MPW - 1) / MPW * MPW;
     uint8_t *mbase = deferred ? (uint8_t *)(((uintptr_t)workspace + deferred_bytes(b, n, m) + 63) & ~(uintptr_t)63) : nullptr;
     const MfmaRegions mr = mfma_regions(b, n, m);
-    unsigned *flag = matrix ? (unsigned *)(mbase + mr.flag) : nullptr;
+    unsigned *flag = matrix ? (pc ? pc->gates : (unsigned *)(mbase + mr.flag)) : nullptr;
     float *meta = (float *)(mbase + mr.meta);
-    hipLaunchKernelGGL(emd_init_kernel, dim3((n + m + 255) / 256, b), dim3(256), 0, s, n, m, multiL, multiR, temp, flag);
-    const int s1 = pick_match_slices(b, n, m), s2 = pick_match_slices(b, m, n);
+    hipLaunchKernelGGL(emd_init_kernel, dim3((n + m + 255) / 256, b), dim3(256), 0, s, n, m, multiL, multiR, temp, flag, pm);
+    const int s1 = pick_match_slices(sb, n, m), s2 = pick_match_slices(sb, m, n);
     const dim3 g1((n + 63) / 64, b), g2((m + 63) / 64, b);
     const dim3 h1((n + PPW - 1) / PPW, b), h2((m + PPW - 1) / PPW, b);               // deferred kernels: 128 points per wave
     const size_t rstride = deferred ? (size_t)(n + m) : (size_t)(n + m) * 2;     // per-cloud stride of a ratio slot
@@ -1600,15 +1630,20 @@ static int approxmatch_impl(int b, int n, int m, const float *xyz1, const float 
     float4 *pk = deferred ? (float4 *)(((uintptr_t)((float *)workspace + NLEVEL * lstride) + 15) & ~(uintptr_t)15) : nullptr;
     float *rec = deferred ? (float *)(pk + (size_t)b * pstride) : nullptr;
     // (the range check first: every kernel of either family looks at its verdict)
-    if (matrix) hipLaunchKernelGGL(emd_mfma_prep_kernel, dim3(b), dim3(1024), 0, s, n, m, xyz1, xyz2, meta, flag);
+    if (matrix) hipLaunchKernelGGL(emd_mfma_prep_kernel, dim3(b), dim3(1024), 0, s, n, m, xyz1, xyz2, meta, flag, pm);
     // (r06, VERDICT r05 #4: the family that is not wanted was moved to a forked side stream -- built, parity-green, measured at
     // cfg5: 2.7323 ms against 2.7315 ms with everything on the caller's stream.  The 31 gated launches sit at the END of the
     // call's sequence, back to back, and their launch latencies overlap each other; r05's "0.13 ms of empty launches" was the
     // rocprof sum of their durations, not time on the call's critical path.  Not kept.)
     if (deferred)
         hipLaunchKernelGGL(emd_pack_init_kernel, dim3((m + 255) / 256, b), dim3(256), 0, s, m, multiR, xyz2, pk + n, pstride,
-                           (const unsigned *)flag);
+                           (const unsigned *)flag, pm);
     int mfma_cost_parts = 0;
+    // The cost partials of a cloud pair: ONE stride for both families, the region's capacity per pair (deferred_bytes).  With a
+    // verdict per pair (dpf_pairwise_emd) pairs of both families share a launch, and strides of their own -- (NP / 64) m1 and
+    // ceil(n / 128) s1, 128 and 64 at 2 048 points -- would lay one pair's partials over another's.
+    static_assert(MPW == PPW && MPW / (32 * MTM) * MSL <= MAXS, "matrix-core cost partials exceed the per-pair region");
+    const int cstride = (n + PPW - 1) / PPW * MAXS;
     if (matrix) {
         // the matrix-core family: gate 0.  Per level: pass 1, pass 2, pass 3 over the live list, then its compaction
         // debug (tests/diag/emd_bisect.py): DPF_EMD_STOP_AFTER=k returns behind the k-th launch of this family
@@ -1623,7 +1658,7 @@ static int approxmatch_impl(int b, int n, int m, const float *xyz1, const float 
         }
         st.ratioR_c = (float *)(mbase + mr.ratioR); st.ratioL_p = (float *)(mbase + mr.ratioL);
         st.count = (int *)(mbase + mr.count); st.counts = (int *)(mbase + mr.counts); st.order = (int *)(mbase + mr.order);
-        st.temp = temp; st.rstride = rstride; st.gate = flag;
+        st.temp = temp; st.rstride = rstride; st.gate = flag; st.pm = pm;
         u4 *recA2_dense = (u4 *)(mbase + mr.recA2d), *recA_s = (u4 *)(mbase + mr.recAs);
         float *rr_s = (float *)(mbase + mr.rrs), *c2soa_s = (float *)(mbase + mr.c2s);
         int *l_s = (int *)(mbase + mr.ls);
@@ -1631,7 +1666,7 @@ static int approxmatch_impl(int b, int n, int m, const float *xyz1, const float 
         hipLaunchKernelGGL(emd_mfma_pack_kernel, dim3((NP + MP + 255) / 256, b), dim3(256), 0, s, st, multiR, xyz1, xyz2,
                            (const float *)meta, recA2_dense, ws, lstride);
         EMD_STOP_CHECK();
-        const int m1 = pick_mfma_slices(b, n, m), m2 = pick_mfma_slices(b, m, n);
+        const int m1 = pick_mfma_slices(sb, n, m), m2 = pick_mfma_slices(sb, m, n);
         const dim3 q1(NP / MPW, b), q2(MP / MPW, b);
         // level j's 4^(j-7) as fp16 powers of two (level_vectors): F down to 2^-14 (a normal fp16 number), f the rest, h = 2^(j-7)
         auto h16 = [](int e) { return (unsigned)((e + 15) << 10); };            // bits of the fp16 number 2^e, -14 <= e <= 15
@@ -1671,12 +1706,18 @@ static int approxmatch_impl(int b, int n, int m, const float *xyz1, const float 
         EMD_STOP_CHECK();
         const dim3 qm(NP / (32 * MTM), b);
         float *costpart_m = rec + (size_t)b * m * 12;
-        if (cost)
-            hipLaunchKernelGGL(emd_mfma_materialize_kernel<true>, qm, dim3(64, m1), 0, s, st, ls, xyz1, (const float *)ws, lstride,
-                               (const u4 *)recA_s, (const float *)rr_s, (const float *)c2soa_s, (const int *)l_s, match, costpart_m);
+        if (!match)
+            hipLaunchKernelGGL((emd_mfma_materialize_kernel<true, false>), qm, dim3(64, m1), 0, s, st, ls, xyz1, (const float *)ws,
+                               lstride, (const u4 *)recA_s, (const float *)rr_s, (const float *)c2soa_s, (const int *)l_s, match,
+                               costpart_m, cstride);
+        else if (cost)
+            hipLaunchKernelGGL((emd_mfma_materialize_kernel<true, true>), qm, dim3(64, m1), 0, s, st, ls, xyz1, (const float *)ws,
+                               lstride, (const u4 *)recA_s, (const float *)rr_s, (const float *)c2soa_s, (const int *)l_s, match,
+                               costpart_m, cstride);
         else
-            hipLaunchKernelGGL(emd_mfma_materialize_kernel<false>, qm, dim3(64, m1), 0, s, st, ls, xyz1, (const float *)ws, lstride,
-                               (const u4 *)recA_s, (const float *)rr_s, (const float *)c2soa_s, (const int *)l_s, match, costpart_m);
+            hipLaunchKernelGGL((emd_mfma_materialize_kernel<false, true>), qm, dim3(64, m1), 0, s, st, ls, xyz1, (const float *)ws,
+                               lstride, (const u4 *)recA_s, (const float *)rr_s, (const float *)c2soa_s, (const int *)l_s, match,
+                               costpart_m, cstride);
         mfma_cost_parts = (int)qm.x * m1;
 #undef EMD_STOP_CHECK
     }
@@ -1690,11 +1731,11 @@ static int approxmatch_impl(int b, int n, int m, const float *xyz1, const float 
         if (deferred) {
             // the packed-VALU family: gate 1 (always when the matrix path is off: flag == nullptr)
             hipLaunchKernelGGL(emd_ratio2_kernel<1>, h1, dim3(64, s1), 0, s, n, m, lvl2, xyz1, xyz2, temp, rb, rstride, pk, pstride,
-                               (const unsigned *)flag);
+                               (const unsigned *)flag, pm);
             hipLaunchKernelGGL(emd_ratio2_kernel<2>, h2, dim3(64, s2), 0, s, n, m, lvl2, xyz1, xyz2, temp, rb, rstride, pk, pstride,
-                               (const unsigned *)flag);
+                               (const unsigned *)flag, pm);
             hipLaunchKernelGGL(emd_match2_kernel, h1, dim3(64, s1), 0, s, n, m, lvl2, xyz1, temp, rb, rstride, (const float4 *)pk, pstride,
-                               (const unsigned *)flag);
+                               (const unsigned *)flag, pm);
             continue;
         }
         hipLaunchKernelGGL(emd_ratio_kernel<1>, g1, dim3(64, s1), 0, s, n, m, lvl2, xyz1, xyz2, temp, rb, rstride);
@@ -1713,19 +1754,23 @@ static int approxmatch_impl(int b, int n, int m, const float *xyz1, const float 
             lp.p[i] = (u64)lo | ((u64)hi << 32);
         }
         hipLaunchKernelGGL(emd_pack_levels_kernel, dim3((m + 255) / 256, b), dim3(256), 0, s, n, m, xyz2,
-                           (const float *)workspace, lstride, rstride, rec, (const unsigned *)flag);
+                           (const float *)workspace, lstride, rstride, rec, (const unsigned *)flag, pm);
         float *costpart = rec + (size_t)b * m * 12;
         if (cost) {
-            hipLaunchKernelGGL(emd_materialize2_kernel<true>, h1, dim3(64, s1), 0, s, n, m, lp, xyz1, (const float *)rec, match,
-                               (const float *)workspace, lstride, rstride, costpart, (const unsigned *)flag);
-            hipLaunchKernelGGL(emd_cost_sum_kernel, dim3(b), dim3(256), 0, s, (int)h1.x * s1, (const float *)costpart, cost,
-                               (const unsigned *)flag, 1u);
+            if (match)
+                hipLaunchKernelGGL((emd_materialize2_kernel<true, true>), h1, dim3(64, s1), 0, s, n, m, lp, xyz1, (const float *)rec,
+                                   match, (const float *)workspace, lstride, rstride, costpart, cstride, (const unsigned *)flag, pm);
+            else
+                hipLaunchKernelGGL((emd_materialize2_kernel<true, false>), h1, dim3(64, s1), 0, s, n, m, lp, xyz1, (const float *)rec,
+                                   match, (const float *)workspace, lstride, rstride, costpart, cstride, (const unsigned *)flag, pm);
+            hipLaunchKernelGGL(emd_cost_sum_kernel, dim3(b), dim3(256), 0, s, (int)h1.x * s1, cstride, (const float *)costpart, cost,
+                               (const unsigned *)flag, 1u, pm);
             if (matrix)
-                hipLaunchKernelGGL(emd_cost_sum_kernel, dim3(b), dim3(256), 0, s, mfma_cost_parts, (const float *)costpart, cost,
-                                   (const unsigned *)flag, 0u);
+                hipLaunchKernelGGL(emd_cost_sum_kernel, dim3(b), dim3(256), 0, s, mfma_cost_parts, cstride, (const float *)costpart,
+                                   cost, (const unsigned *)flag, 0u, pm);
         } else {
-            hipLaunchKernelGGL(emd_materialize2_kernel<false>, h1, dim3(64, s1), 0, s, n, m, lp, xyz1, (const float *)rec, match,
-                               (const float *)workspace, lstride, rstride, costpart, (const unsigned *)flag);
+            hipLaunchKernelGGL((emd_materialize2_kernel<false, true>), h1, dim3(64, s1), 0, s, n, m, lp, xyz1, (const float *)rec,
+                               match, (const float *)workspace, lstride, rstride, costpart, cstride, (const unsigned *)flag, pm);
         }
     }
     return (int)hipGetLastError();
@@ -1755,9 +1800,9 @@ extern "C" int dpf_debug_emd_exponents(int n, int m, const float *xyz1, const fl
     }
     st.ratioR_c = (float *)(mbase + mr.ratioR); st.ratioL_p = (float *)(mbase + mr.ratioL);
     st.count = (int *)(mbase + mr.count); st.counts = (int *)(mbase + mr.counts); st.order = (int *)(mbase + mr.order);
-    st.temp = nullptr; st.rstride = (size_t)(n + m); st.gate = flag;
+    st.temp = nullptr; st.rstride = (size_t)(n + m); st.gate = flag; st.pm = PairMap{1, 1, 0};
     u4 *recA2_dense = (u4 *)(mbase + mr.recA2d);
-    hipLaunchKernelGGL(emd_mfma_prep_kernel, dim3(1), dim3(1024), 0, s, n, m, xyz1, xyz2, meta, flag);
+    hipLaunchKernelGGL(emd_mfma_prep_kernel, dim3(1), dim3(1024), 0, s, n, m, xyz1, xyz2, meta, flag, st.pm);
     hipLaunchKernelGGL(emd_mfma_pack_kernel, dim3((NP + MP + 255) / 256, 1), dim3(256), 0, s, st, 1.0f, xyz1, xyz2, (const float *)meta,
                        recA2_dense, (float *)workspace, (size_t)(n + m));
     const int ex = 2 * (level_j - 7), eF = ex < -14 ? -14 : ex;
@@ -1796,6 +1841,37 @@ extern "C" int dpf_approxmatch_cost_ws(int b, int n, int m, const float *xyz1, c
     if (!cost || !workspace || (b > 0 && n > 0 && m > 0 && workspace_bytes < dpf_approxmatch_workspace_bytes(b, n, m)))
         return DPF_EINVAL;
     return approxmatch_impl(b, n, m, xyz1, xyz2, match, temp, cost, workspace, workspace_bytes, stream);
+}
+
+// The pairwise matrix: the rows x n2 pairs of one launch are the batch of the deferred path (pair i n2 + j reads clouds1[i] and
+// clouds2[j] in place: PairMap {n2, n2, 1}), each with its own family verdict, and no matching is written.  The slices are those
+// the batched entries pick for PAIRWISE_SLICE_B clouds -- a function of (n, m) alone, so an entry's bits do not depend on how the
+// matrix is cut into launches.  (64 clouds: 4 slices at 2 048 points, 1 from 8 192 -- the launches of a matrix hold hundreds of
+// pairs, and 4 waves per 128 points keep a 64-pair launch at the 4 096 waves the batched choice aims for.)
+// Workspace: [the deferred path's (rows n2 pairs) | temp: rows n2 x 2 (n + m) floats | the verdicts: rows n2 words].
+constexpr int PAIRWISE_SLICE_B = 64;
+static size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
+
+extern "C" size_t dpf_pairwise_emd_workspace_bytes(int rows, int n2, int n, int m) {
+    if (rows <= 0 || n2 <= 0 || n <= 0 || m <= 0 || (long)rows * n2 > 65535) return 0;
+    const int P = rows * n2;
+    return align64(dpf_approxmatch_workspace_bytes(P, n, m)) + align64((size_t)P * 2 * ((size_t)n + m) * sizeof(float)) +
+           (size_t)P * sizeof(unsigned);
+}
+
+extern "C" int dpf_pairwise_emd(int rows, int n2, int n, int m, const float *clouds1, const float *clouds2, float *cost,
+                                void *workspace, size_t workspace_bytes, dpf_stream_t stream) {
+    if (rows < 0 || n2 < 0 || n <= 0 || m <= 0) return DPF_EINVAL;
+    if (rows == 0 || n2 == 0) return 0;
+    if (!clouds1 || !clouds2 || !cost || !workspace) return DPF_EINVAL;
+    if ((long)rows * n2 > 65535) return DPF_ENOSUP;                       // the pairs are grid y of the per-pair kernels
+    if (workspace_bytes < dpf_pairwise_emd_workspace_bytes(rows, n2, n, m)) return DPF_EINVAL;
+    const int P = rows * n2;
+    const size_t wb = align64(dpf_approxmatch_workspace_bytes(P, n, m));
+    float *temp = (float *)((uint8_t *)workspace + wb);
+    unsigned *gates = (unsigned *)((uint8_t *)temp + align64((size_t)P * 2 * ((size_t)n + m) * sizeof(float)));
+    const PairCall pc{PairMap{n2, n2, 1}, gates, PAIRWISE_SLICE_B};
+    return approxmatch_impl(P, n, m, clouds1, clouds2, nullptr, temp, cost, workspace, wb, stream, &pc);
 }
 
 extern "C" int dpf_approxmatch(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *temp,

@@ -4,6 +4,9 @@
   EMD_CD (:48-82)                                   -- per-pair Chamfer of two equally long sets, batched
   _pairwise_EMD_CD_ (:85-121)                       -- the (N_sample, N_ref) Chamfer and EMD matrices; the only caller of
                                                        match_cost in the reference
+  knn (:125-154), lgan_mmd_cov (:157-169)           -- 1-NN accuracy, MMD and COV over those matrices (tensor arithmetic)
+  compute_all_metrics (:172-200)                    -- the generation metrics (MMD / COV / 1-NNA, CD and EMD), its three matrix
+                                                       pairs from networks.utils.pairwise_CD + pairwise_EMD
 
 Same signatures, return structures and values as the reference's loops.  What differs is how a row is fed: the reference
 expands sample i to (batch, n, 3) and copies it (`.contiguous()`) for every block of references; here the Chamfer launch
@@ -14,6 +17,7 @@ is no CPU or tensor-op fallback in this package, so both values of the flag run 
 import torch
 
 from ..networks.utils import distChamferCUDA, emd_approx, chamfer_per_cloud, chamfer_cd_per_cloud  # noqa: F401
+from ..networks.utils import pairwise_CD, pairwise_EMD
 from .._lib import lib, check, current_stream
 
 
@@ -60,3 +64,71 @@ def _pairwise_EMD_CD_(sample_pcs, ref_pcs, batch_size, accelerated_cd=True):
                       "chamfer_reduce")
                 all_emd[i, r0:r1] = emd_approx(sample_pcs[i].unsqueeze(0).expand(nb, -1, -1).contiguous(), ref_pcs[r0:r1])
     return all_cd, all_emd
+
+
+def knn(Mxx, Mxy, Myy, k, sqrt=False):
+    """k-NN two-sample classifier, leave-one-out (:125-154): the clouds of x are labelled 1, those of y 0, and every cloud is
+    predicted 1 when at least k / 2 of its k nearest other clouds (smallest entries of its column of the joint distance
+    matrix) carry label 1.  Returns the confusion counts tp / fp / fn / tn, precision, recall, the per-class accuracies acc_t
+    (of x) and acc_f (of y) and the overall accuracy acc, each a 0-d tensor of Mxx's dtype and device -- the same float32
+    operations as the reference, in the same order."""
+    n0, n1 = Mxx.size(0), Myy.size(0)
+    label = torch.cat((torch.ones(n0), torch.zeros(n1))).to(Mxx)
+    M = torch.cat((torch.cat((Mxx, Mxy), 1), torch.cat((Mxy.transpose(0, 1), Myy), 1)), 0)
+    if sqrt:
+        M = M.abs().sqrt()
+    self_excluded = M + torch.diag(float("inf") * torch.ones(n0 + n1).to(Mxx))
+    _, idx = self_excluded.topk(k, 0, False)                               # (k, n0 + n1): every column's k nearest rows
+    votes = torch.zeros(n0 + n1).to(Mxx)
+    for i in range(k):
+        votes = votes + label.index_select(0, idx[i])
+    pred = torch.ge(votes, (float(k) / 2) * torch.ones(n0 + n1).to(Mxx)).float()
+    tp, fp = (pred * label).sum(), (pred * (1 - label)).sum()
+    fn, tn = ((1 - pred) * label).sum(), ((1 - pred) * (1 - label)).sum()
+    return {
+        'tp': tp, 'fp': fp, 'fn': fn, 'tn': tn,
+        'precision': tp / (tp + fp + 1e-10),
+        'recall': tp / (tp + fn + 1e-10),
+        'acc_t': tp / (tp + fn + 1e-10),
+        'acc_f': tn / (tn + fp + 1e-10),
+        'acc': torch.eq(label, pred).float().mean(),
+    }
+
+
+def lgan_mmd_cov(all_dist):
+    """MMD and coverage of an (N_sample, N_ref) distance matrix (:157-169): lgan_mmd = mean over the references of the distance
+    to the nearest sample, lgan_mmd_smp = mean over the samples of the distance to the nearest reference, lgan_cov = share of
+    the references that are the nearest reference of some sample.  0-d tensors of all_dist's dtype and device."""
+    N_ref = all_dist.size(1)
+    nearest_ref_val, nearest_ref = torch.min(all_dist, dim=1)
+    nearest_smp_val, _ = torch.min(all_dist, dim=0)
+    covered = float(nearest_ref.unique().view(-1).size(0))
+    return {
+        'lgan_mmd': nearest_smp_val.mean(),
+        'lgan_cov': torch.tensor(covered / float(N_ref)).to(all_dist),
+        'lgan_mmd_smp': nearest_ref_val.mean(),
+    }
+
+
+def _pairwise_matrices(clouds1, clouds2, batch_size):
+    """(CD, EMD) matrices of every cloud of clouds1 against every cloud of clouds2: one matrix launch per chunk for each, both
+    sets read in place (what _pairwise_EMD_CD_ returns, without its per-row loop and without forming any matching)."""
+    return pairwise_CD(clouds1, clouds2, bs=batch_size), pairwise_EMD(clouds1, clouds2, bs=batch_size)
+
+
+def compute_all_metrics(sample_pcs, ref_pcs, batch_size, accelerated_cd=False):
+    """The generation metrics of the reference (:172-200): MMD and COV (lgan_mmd_cov) from the (sample, reference) matrices
+    and 1-NN accuracy (knn, k = 1) from those plus the (reference, reference) and (sample, sample) matrices, for Chamfer and
+    approximate EMD.  Keys "lgan_mmd-CD", "lgan_cov-CD", "lgan_mmd_smp-CD", the same for EMD, "1-NN-CD-acc_t",
+    "1-NN-CD-acc_f", "1-NN-CD-acc" and the same for EMD.  The reference's orientation is kept: the cross matrices are computed
+    as (reference, sample) and transposed for lgan_mmd_cov, and approx-EMD is not symmetric in its operands.  `batch_size`
+    bounds the pairs per launch; `accelerated_cd` is accepted and ignored (module docstring).  No autograd (pairwise_EMD)."""
+    results = {}
+    M_rs_cd, M_rs_emd = _pairwise_matrices(ref_pcs, sample_pcs, batch_size)
+    for metric, M in (("CD", M_rs_cd), ("EMD", M_rs_emd)):
+        results.update({"%s-%s" % (k, metric): v for k, v in lgan_mmd_cov(M.t()).items()})
+    M_rr_cd, M_rr_emd = _pairwise_matrices(ref_pcs, ref_pcs, batch_size)
+    M_ss_cd, M_ss_emd = _pairwise_matrices(sample_pcs, sample_pcs, batch_size)
+    for metric, (M_rr, M_rs, M_ss) in (("CD", (M_rr_cd, M_rs_cd, M_ss_cd)), ("EMD", (M_rr_emd, M_rs_emd, M_ss_emd))):
+        results.update({"1-NN-%s-%s" % (metric, k): v for k, v in knn(M_rr, M_rs, M_ss, 1, sqrt=False).items() if 'acc' in k})
+    return results

@@ -1,6 +1,6 @@
 """Chamfer call sites of the reference's lib/networks/utils.py (metrics half):
 distChamferCUDA (:34-35), f_score (:38-42), pairwise_CD (:90-117), and
-emd_approx (lib/metrics/evaluation_metrics.py:26-31)."""
+emd_approx (lib/metrics/evaluation_metrics.py:26-31) with its pairwise matrix, pairwise_EMD (the EMD half of :85-121)."""
 import torch
 
 from ..metrics.StructuralLosses.nn_distance import nn_distance
@@ -156,6 +156,64 @@ def emd_approx(sample, ref):
     B, N, N_ref = sample.size(0), sample.size(1), ref.size(1)
     assert N == N_ref, "Not sure what would EMD do in this case"
     return match_cost(sample, ref) / float(N)
+
+
+def pairwise_EMD(clouds1, clouds2, bs=512, shard_rows=False):
+    """(N1, N2) matrix of approximate EMDs, out[i, j] = emd_approx(clouds1[i:i+1], clouds2[j:j+1]) to the approx-EMD tolerance
+    contract (the EMD half of lib/metrics/evaluation_metrics.py:85-121, what compute_all_metrics builds its EMD numbers on).
+
+    dpf_pairwise_emd: every pair of a launch is one cloud pair of the approx-EMD passes, both sets read in place, and no matching
+    is written (the reference's loop expands a copy of clouds1[i] per block and writes a (b, n, n) matching per call).  The cost
+    is divided by float(n) in fp32 as emd_approx does.  `bs` bounds the pairs per launch, and with them the workspace (about
+    1.2 MB per pair at 2 048 points); an entry's bits do not depend on it.  Each pair chooses its kernel family from its own
+    two clouds: an out-of-range or NaN cloud changes only its own entries.
+    shard_rows: under torch.distributed every rank computes its contiguous block of rows (distributed.shard_bounds) and the
+    matrix is all-gathered, as pairwise_CD does.
+    No autograd: match_cost's backward needs the matching, which this path never forms -- inputs that would record a graph
+    raise."""
+    from .._lib import lib, check, current_stream
+    if not (clouds1.is_cuda and clouds2.is_cuda):
+        raise RuntimeError("pairwise_EMD needs CUDA tensors")
+    if clouds1.dtype != torch.float32 or clouds2.dtype != torch.float32:
+        raise RuntimeError("pairwise_EMD needs float32 clouds")
+    if torch.is_grad_enabled() and (clouds1.requires_grad or clouds2.requires_grad):
+        raise RuntimeError("pairwise_EMD has no backward (it never forms the matching): call it under torch.no_grad() or on "
+                           "tensors that do not require grad")
+    if clouds1.dim() != 3 or clouds2.dim() != 3 or clouds1.shape[2] != 3 or clouds2.shape[2] != 3:
+        raise RuntimeError("pairwise_EMD needs point-major (N, n, 3) clouds, got %s and %s"
+                           % (tuple(clouds1.shape), tuple(clouds2.shape)))
+    clouds1, clouds2 = clouds1.contiguous(), clouds2.contiguous()
+    N1, n = clouds1.shape[0], clouds1.shape[1]
+    N2, m = clouds2.shape[0], clouds2.shape[1]
+    assert n == m, "Not sure what would EMD do in this case"
+    dev = clouds1.device
+    lo, hi = 0, N1
+    if shard_rows:
+        from .. import distributed as D
+        lo, hi = D.shard_bounds(N1)
+    emds = torch.empty((hi - lo, N2), dtype=torch.float32, device=dev)
+    if hi > lo and N2 > 0 and n > 0:
+        cols = max(1, min(N2, bs, 65535))                       # rows * cols pairs per launch: <= bs, and <= 65535 (grid y)
+        rows = max(1, min(hi - lo, bs // cols, 65535 // cols))
+        with torch.cuda.device(dev):
+            st = current_stream()
+            nbytes = lib().dpf_pairwise_emd_workspace_bytes(rows, cols, n, m)
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            blk = torch.empty((rows * cols,), dtype=torch.float32, device=dev) if cols < N2 else None
+            for r0 in range(lo, hi, rows):
+                nr = min(rows, hi - r0)
+                for c0 in range(0, N2, cols):
+                    nc = min(cols, N2 - c0)
+                    dst = emds[r0 - lo] if blk is None else blk
+                    check(lib().dpf_pairwise_emd(nr, nc, n, m, clouds1[r0].data_ptr(), clouds2[c0].data_ptr(), dst.data_ptr(),
+                                                 ws.data_ptr(), nbytes, st), "pairwise_emd")
+                    if blk is not None:
+                        emds[r0 - lo:r0 - lo + nr, c0:c0 + nc] = blk[:nr * nc].view(nr, nc)
+        emds.div_(float(n))                                     # (the fp32 division of emd_approx, in place)
+    if shard_rows:
+        from .. import distributed as D
+        emds = D.gather_clouds(emds)
+    return emds
 
 
 # ----------------------------------------------------------------------------------------------------------------

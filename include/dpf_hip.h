@@ -186,6 +186,22 @@ size_t dpf_pairwise_cd_workspace_bytes(int n1, int n2, int n, int m);
 int dpf_pairwise_cd(int n1, int n2, int n, int m, const float *clouds1, const float *clouds2, float *cds,
                     void *workspace, size_t workspace_bytes, dpf_stream_t stream);
 
+/* The EMD half of _pairwise_EMD_CD_, lib/metrics/evaluation_metrics.py:85-121 (compute_all_metrics' three matrices,
+ * :172-200): cost[i * n2 + j] = sum match * |x1 - x2| of the approximate matching of seta = clouds1[i], setb = clouds2[j] --
+ * what dpf_approxmatch_cost_ws returns for that pair, NOT divided by n -- for all rows x n2 pairs in one call.  The reference's
+ * per-i `expand + contiguous + match_cost` loop and its (b, m, n) matchings disappear: clouds1 (rows, n, 3) and clouds2
+ * (n2, m, 3), point-major fp32, are read in place, and no matching is written anywhere (the last pass of either kernel family
+ * only sums match * distance).  The pairs are the batch of dpf_approxmatch_ws's deferred path; each pair picks its kernel family
+ * itself (matrix-core when its own two clouds are in range and finite, else packed-VALU), so an out-of-range or NaN cloud changes
+ * only its own entries.  The slice counts depend on (n, m) alone: an entry has the same bits whichever rows / columns the call
+ * covers (a row-sharded or chunked evaluation computes the same matrix).  dpf_emd_set_matrix_path(0) / DPF_EMD_MATRIX=0 apply
+ * as to dpf_approxmatch_ws.  Tolerance class of dpf_approxmatch_cost_ws (cost 1e-4 against the reference's kernels).
+ * rows * n2 <= 65535 (DPF_ENOSUP above: the caller chunks).  workspace: dpf_pairwise_emd_workspace_bytes bytes, caller-owned,
+ * no state across calls -- dpf_approxmatch_workspace_bytes(rows * n2, n, m) + 8 (n + m) + 4 bytes per pair. */
+size_t dpf_pairwise_emd_workspace_bytes(int rows, int n2, int n, int m);
+int dpf_pairwise_emd(int rows, int n2, int n, int m, const float *clouds1, const float *clouds2, float *cost,
+                     void *workspace, size_t workspace_bytes, dpf_stream_t stream);
+
 /* ------------------------------------------------------------------------ *
  * Per-point conditional affine-coupling flow (eval-mode BatchNorm), i.e.
  * LocalCondRNVPDecoder.forward (lib/networks/decoders.py:54-72) over
