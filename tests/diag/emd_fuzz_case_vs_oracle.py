@@ -8,8 +8,8 @@ from dpf_nets_amd._lib import lib
 from dpf_nets_amd.metrics.StructuralLosses import StructuralLossesBackend as BK
 from oracle import structural as S
 seed, index = int(sys.argv[1]), int(sys.argv[2])
-if os.environ.get("EMD_CASE_GENERATOR") == "suite":      # tests/test_gpu_emd.py::emd_fuzz_case (tools/emd_oracle_fuzz.py's cases)
-    from tests.test_gpu_emd import emd_fuzz_case
+if os.environ.get("EMD_CASE_GENERATOR") == "suite":      # tests/emd_cases.py::emd_fuzz_case (tools/emd_oracle_fuzz.py's cases)
+    from tests.emd_cases import emd_fuzz_case
     rng = np.random.default_rng(seed)
     for it in range(index + 1):
         a, b, kind = emd_fuzz_case(rng)

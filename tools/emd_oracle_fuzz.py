@@ -1,4 +1,4 @@
-"""The in-suite approx-EMD fuzz (tests/test_gpu_emd.py::emd_fuzz_case: nine cloud kinds, ragged shapes) WITHOUT its time box: N cases of
+"""The in-suite approx-EMD fuzz (tests/emd_cases.py::emd_fuzz_case: nine cloud kinds, ragged shapes) at any case count: N cases of
 the default (matrix-core) path and every fourth also of the packed-VALU kernels against the CPU oracle -- and, per cloud, the SAME
 auction in float64 (numpy), which tells how well the input is conditioned: the fp32 oracle's own distance from exact arithmetic.
 The auction divides by (1e-9 + a sum of weights); a point whose neighbours have all been consumed has a sum of that size, and fp32
@@ -11,7 +11,7 @@ import os, sys, time
 import numpy as np, torch
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, root)
-from tests.test_gpu_emd import emd_fuzz_case
+from tests.emd_cases import emd_fuzz_case
 from dpf_nets_amd._lib import lib
 from dpf_nets_amd.metrics.StructuralLosses import StructuralLossesBackend as BK
 from oracle import structural as S
