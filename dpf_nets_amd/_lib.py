@@ -34,6 +34,9 @@ SIGNATURES = {
     "dpf_emd_set_matrix_path": (_i, [_i]),
     "dpf_approxmatch_ws": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dpf_approxmatch_cost_ws": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dpf_approxmatch_costonly_ws": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dpf_matchcostgrad_recompute_workspace_bytes": (_sz, [_i, _i, _i]),
+    "dpf_matchcostgrad_recompute_ws": (_i, [_i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
     "dpf_matchcost": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dpf_matchcostgrad_workspace_bytes": (_sz, [_i, _i, _i]),
     "dpf_matchcostgrad_ws": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -21,6 +21,7 @@ from ..._lib import lib, check, current_stream
 NN_IMPL = os.environ.get("DPF_CHAMFER_IMPL", "auto")
 EMD_GRAD_TWO_PASS = bool(int(os.environ.get("DPF_EMD_GRAD_TWO_PASS", "0")))   # 1: separate grad1 / grad2 kernels
 EMD_RMW = bool(int(os.environ.get("DPF_EMD_RMW", "0")))   # 1: the reference's per-level read-modify-write of `match`
+EMD_LEAN_GRAD = bool(int(os.environ.get("DPF_EMD_LEAN_GRAD", "0")))   # 1: match_cost never stores the matching (match_cost_lean)
 
 
 def nn_impl_entry(impl):
@@ -173,6 +174,42 @@ def ApproxMatchCost(set_d, set_q):
         check(lib().dpf_approxmatch_cost_ws(b, n, m, set_d.data_ptr(), set_q.data_ptr(), match.data_ptr(), temp.data_ptr(),
                                             cost.data_ptr(), ws.data_ptr(), nbytes, current_stream()), "approxmatch_cost_ws")
     return [match, temp, cost]
+
+
+def ApproxMatchCostOnly(set_d, set_q):
+    """ApproxMatchCost without the matching -> [temp, cost (B,), saved]: same bits of `temp[:, :n+m]` and `cost`, nothing of size
+    n*m allocated or written (dpf_approxmatch_costonly_ws).  `saved` is the call's workspace: the state MatchCostGradRecompute
+    rebuilds the matching from -- keep it, and the two clouds, unchanged until then."""
+    _check_input(set_d, "set_d"); _check_input(set_q, "set_q")
+    b, n, m = _dims(set_d, set_q)
+    dev = set_d.device
+    temp = torch.empty((b, (n + m) * 2), dtype=torch.float32, device=dev)
+    cost = torch.empty((b,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        nbytes = lib().dpf_approxmatch_workspace_bytes(b, n, m)
+        saved = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+        check(lib().dpf_approxmatch_costonly_ws(b, n, m, set_d.data_ptr(), set_q.data_ptr(), temp.data_ptr(), cost.data_ptr(),
+                                                saved.data_ptr(), nbytes, current_stream()), "approxmatch_costonly_ws")
+    return [temp, cost, saved]
+
+
+def MatchCostGradRecompute(set_d, set_q, saved):
+    """MatchCostGrad without a stored matching -> [grad1 (B,n,3), grad2 (B,m,3)]: the weights are rebuilt in registers from
+    `saved` (ApproxMatchCostOnly of the same clouds), which is only read (dpf_matchcostgrad_recompute_ws)."""
+    _check_input(set_d, "set_d"); _check_input(set_q, "set_q"); _check_input(saved, "saved", torch.uint8)
+    b, n, m = _dims(set_d, set_q)
+    dev = set_d.device
+    grad1 = torch.empty((b, n, 3), dtype=torch.float32, device=dev)
+    grad2 = torch.empty((b, m, 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        if saved.device != dev or saved.numel() < lib().dpf_approxmatch_workspace_bytes(b, n, m):
+            raise RuntimeError("MatchCostGradRecompute: `saved` is not ApproxMatchCostOnly's workspace of these clouds")
+        nbytes = lib().dpf_matchcostgrad_recompute_workspace_bytes(b, n, m)
+        scratch = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+        check(lib().dpf_matchcostgrad_recompute_ws(b, n, m, set_d.data_ptr(), set_q.data_ptr(), saved.data_ptr(), saved.numel(),
+                                                   grad1.data_ptr(), grad2.data_ptr(), scratch.data_ptr(), nbytes,
+                                                   current_stream()), "matchcostgrad_recompute_ws")
+    return [grad1, grad2]
 
 
 def MatchCost(set_d, set_q, match):

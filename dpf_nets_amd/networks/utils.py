@@ -4,7 +4,7 @@ emd_approx (lib/metrics/evaluation_metrics.py:26-31) with its pairwise matrix, p
 import torch
 
 from ..metrics.StructuralLosses.nn_distance import nn_distance
-from ..metrics.StructuralLosses.match_cost import match_cost
+from ..metrics.StructuralLosses.match_cost import match_cost, match_cost_lean
 
 
 def distChamferCUDA(x, y):
@@ -158,6 +158,14 @@ def emd_approx(sample, ref):
     return match_cost(sample, ref) / float(N)
 
 
+def emd_approx_lean(sample, ref):
+    """emd_approx through match_cost_lean: the same value, and a backward that rebuilds the matching's weights instead of
+    reading a stored (B, N, N) matching (metrics/StructuralLosses/match_cost.py, MatchCostLeanFunction)."""
+    B, N, N_ref = sample.size(0), sample.size(1), ref.size(1)
+    assert N == N_ref, "Not sure what would EMD do in this case"
+    return match_cost_lean(sample, ref) / float(N)
+
+
 def pairwise_EMD(clouds1, clouds2, bs=512, shard_rows=False):
     """(N1, N2) matrix of approximate EMDs, out[i, j] = emd_approx(clouds1[i:i+1], clouds2[j:j+1]) to the approx-EMD tolerance
     contract (the EMD half of lib/metrics/evaluation_metrics.py:85-121, what compute_all_metrics builds its EMD numbers on).
@@ -169,8 +177,9 @@ def pairwise_EMD(clouds1, clouds2, bs=512, shard_rows=False):
     two clouds: an out-of-range or NaN cloud changes only its own entries.
     shard_rows: under torch.distributed every rank computes its contiguous block of rows (distributed.shard_bounds) and the
     matrix is all-gathered, as pairwise_CD does.
-    No autograd: match_cost's backward needs the matching, which this path never forms -- inputs that would record a graph
-    raise."""
+    No autograd: the pairwise entry keeps no state for a backward -- inputs that would record a graph raise.  (The batched
+    function no longer needs a stored matching for its gradients: emd_approx_lean / match_cost_lean rebuild the weights from the
+    forward's workspace.  The pairwise entry has no such backward.)"""
     from .._lib import lib, check, current_stream
     if not (clouds1.is_cuda and clouds2.is_cuda):
         raise RuntimeError("pairwise_EMD needs CUDA tensors")

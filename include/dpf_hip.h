@@ -135,6 +135,38 @@ int dpf_approxmatch_cost_ws(int b, int n, int m, const float *xyz1, const float 
                             float *match, float *temp, float *cost, void *workspace,
                             size_t workspace_bytes, dpf_stream_t stream);
 
+/* dpf_approxmatch_cost_ws without the matching: no `match` argument, nothing of size n*m written or allocated.  The launches,
+ * the slices and every operation of the sums are those of dpf_approxmatch_cost_ws (its last pass runs without its stores), so
+ * `cost` and temp[:, :n+m] carry the same bits on the same input -- both kernel families, and clouds the device hands to the
+ * packed-VALU family (out of range, not finite).  workspace: dpf_approxmatch_workspace_bytes, required.
+ * On return the workspace is the SAVED STATE of dpf_matchcostgrad_recompute_ws, which reads
+ *   - the nine per-level ratio slots [ratioL (n) | ratioR (m)] per cloud (the front of the workspace);
+ *   - the packed-VALU family's materialisation records (xyz2, ratioR of the nine levels: 12 floats per point of cloud 2), behind
+ *     the passes' packed (x, y, z, w) records;
+ *   - of the matrix-core regions: recB1 (cloud 1's operand records), recAs / rrs / c2s / ls (cloud 2's operand records, per-level
+ *     ratioR, coordinates and row numbers in the order the points left the auction) and counts (the levels' list lengths);
+ *   - the flag region: word 0 the device's per-call verdict (1: packed-VALU), word 1 the matrix-path setting of THIS call
+ *     (written by this entry only).
+ * The caller keeps the workspace unchanged, and xyz1 / xyz2 as they were, until the backward has run. */
+int dpf_approxmatch_costonly_ws(int b, int n, int m, const float *xyz1, const float *xyz2,
+                                float *temp, float *cost, void *workspace, size_t workspace_bytes,
+                                dpf_stream_t stream);
+
+/* The gradients of dpf_matchcostgrad with the matching REBUILT, tile by tile in registers, from the state
+ * dpf_approxmatch_costonly_ws left in `saved_workspace`: no (b, m, n) tensor exists at any time.  The rebuilt weights are the
+ * bits the materialising pass would have stored (the same level loop on the same operands: the same MFMAs for the matrix-core
+ * family, the same packed-VALU level sum for the other); only the order of the gradients' sums differs from
+ * dpf_matchcostgrad_ws.  The family is the one the forward ran: read from the saved verdict and setting, not from
+ * dpf_emd_set_matrix_path at the time of this call.  saved_workspace is only read (a second call returns the same bits);
+ * scratch (dpf_matchcostgrad_recompute_workspace_bytes: 12 bytes per 64-column block and row, 3 / (16 n) of the matching)
+ * takes grad2's per-column-block partial sums, added in a fixed order: deterministic, no atomics.  Allocates nothing, does not
+ * synchronise, safe under stream capture. */
+size_t dpf_matchcostgrad_recompute_workspace_bytes(int b, int n, int m);
+int dpf_matchcostgrad_recompute_ws(int b, int n, int m, const float *xyz1, const float *xyz2,
+                                   const void *saved_workspace, size_t saved_bytes,
+                                   float *grad1, float *grad2, void *scratch, size_t scratch_bytes,
+                                   dpf_stream_t stream);
+
 /* replaces matchcost(...)       src/approxmatch.cuh:7, approxmatch.cu:309-316.
  * out: (b,) = sum_{l,k} match[b,l,k] * |xyz1[b,k]-xyz2[b,l]|_2. */
 int dpf_matchcost(int b, int n, int m, const float *xyz1, const float *xyz2,
