@@ -39,11 +39,11 @@ __global__ __launch_bounds__(PACK_THREADS) void gprior_pack_kernel(int nets, int
         if (o < (size_t)K * nf) {
             const int k = (int)(o / nf), j = (int)(o - (size_t)k * nf);
             v = c[(size_t)j * K + k];
-        } else if ((o -= (size_t)K * nf) < (size_t)nf) {
-            v = gam[o] / sqrtf(rv[o] + bn_eps);
+        } else if ((o -= (size_t)K * nf) < (size_t)nf) {     // a, c in double, rounded once: in fp32 the sum, the root and the quotient
+            v = (float)((double)gam[o] / sqrt((double)rv[o] + (double)bn_eps));      // each round (up to 2.5 u; runs once per weight version)
         } else if ((o -= nf) < (size_t)nf) {
-            const float a = gam[o] / sqrtf(rv[o] + bn_eps);
-            v = bet[o] - rm[o] * a;
+            const double a = (double)gam[o] / sqrt((double)rv[o] + (double)bn_eps);
+            v = (float)((double)bet[o] - (double)rm[o] * a);
         } else if ((o -= nf) < (size_t)nf * K) {
             const int j = (int)(o / K), i = (int)(o - (size_t)j * K);
             v = w1[(size_t)i * nf + j];

@@ -1,7 +1,8 @@
 """dpf_adam_step (csrc/adam.hip): the fused AMSGrad-Adam step of SURVEY 8(f) rank 4 against the reference's op sequence
 (lib/networks/optimizers.py:52-74 as networks/optimizers.py::Adam._update restates it, itself pinned bit for bit on the
 reference's class by tests/golden/optimizer.npz): bit-identical over several steps, with and without AMSGrad / weight decay,
-on sizes with and without a vector tail; and through the optimizer class on a flattened decoder."""
+on sizes with and without a vector tail, below and past the launch's grid cap (2048 workgroups x 256 float4: the grid-stride loop
+takes a second trip from n = 2 097 153 on); and through the optimizer class on a flattened decoder."""
 import math
 
 import pytest
@@ -17,7 +18,12 @@ def _gpu():
     return networks
 
 
-@pytest.mark.parametrize("n", [1 << 20, 4099, 3])
+# past the cap: between one and two trips (+ 1 tail element); two full trips, 1000 float4 of a third and a 3-element tail.
+# 1, 2, 5, 1023, 1025: the tail alone, a tail behind one float4, behind 255 and 256 of them.
+ADAM_SIZES = [1 << 20, 4099, 3, 4 * (2048 * 256 + 77777) + 1, 4 * (2 * 2048 * 256 + 1000) + 3, 1, 2, 5, 1023, 1025]
+
+
+@pytest.mark.parametrize("n", ADAM_SIZES)
 @pytest.mark.parametrize("amsgrad", [True, False])
 @pytest.mark.parametrize("wd", [1e-6, 0.0])
 def test_fused_adam_step_is_bitwise_the_op_sequence(n, amsgrad, wd):
@@ -32,7 +38,7 @@ def test_fused_adam_step_is_bitwise_the_op_sequence(n, amsgrad, wd):
     ref = [t.clone() for t in (p, m, v, vm)]
     got = [t.clone() for t in (p, m, v, vm)]
     lr, b1, b2, eps = 2.56e-4, 0.9, 0.999, 1e-8
-    for step in range(1, 6):
+    for step in range(1, 4 if n > (1 << 21) else 6):
         g = torch.randn(n, device="cuda", generator=gen) * (0.3 ** step)
         nets.Adam._update([ref[0]], [g], [ref[1]], [ref[2]], [ref[3]] if amsgrad else None, step, lr, b1, b2, eps, wd, amsgrad)
         rc = lib().dpf_adam_step(n, got[0].data_ptr(), g.data_ptr(), got[1].data_ptr(), got[2].data_ptr(),
