@@ -470,7 +470,7 @@ constexpr int EMD_GMAX = 11;              // finest grid 2^-11: T >= -8
 constexpr int RECQ = 4;                   // 16-byte quarters per point record: [MFMA 1: K 0..7 | K 8..15 | MFMA 2: K 0..7 | K 8..15]
 constexpr int METAF = 8;                  // floats of per-cloud meta: centroid (3), out-of-range flag, 2^g, T
 
-__device__ __forceinline__ int round_up(int v, int q) { return (v + q - 1) / q * q; }
+__host__ __device__ __forceinline__ int round_up(int v, int q) { return (v + q - 1) / q * q; }
 
 // One workgroup per cloud: cloud 1's centroid (fixed-order sums), the grid exponent g from the largest centred, scaled
 // coordinate of either cloud, and whether every point of both clouds is in range
@@ -689,81 +689,23 @@ __device__ __forceinline__ f16acc opaque_zero() {
     asm volatile("" : "+v"(z));
     return z;
 }
-#ifndef EMD_DBG
-#define EMD_DBG 0          // A/B builds of r06's hunt (tests/diag/emd_rows_probe.py, emd_chain_mismatch.py; all of them flickered or
-                           // agreed exactly as the plain build did -- DESIGN 4.6): 1 64 wait states behind the chain, 2 no chaining,
-                           // 4 tiles serialised, 8 chained against unchained in every call, mismatches recorded
-#endif
-#if EMD_DBG & 8
-__device__ unsigned g_emd_dbg_n;
-__device__ float g_emd_dbg[16 * 8];
-#endif
+// (up to commit 5c94248 this function and the prefetch fences below carried r06's A/B switches -- EMD_DBG, EMD_PIN_LOADS; every one
+// of them flickered or agreed exactly as the plain build did: DESIGN 4.6, profiles/r06_emd_bisect.txt)
 __device__ __forceinline__ f16acc pair_exponents(const Frag &rows, const Frag &cols, const f16acc &zacc) {
-#if EMD_DBG & 8
-    {   // chained against unchained, mismatches recorded
-        const f16acc i1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(rows.q1, cols.q1, zacc, 0, 0, 0);
-        const f16acc ch = __builtin_amdgcn_mfma_f32_32x32x16_f16(rows.q2, cols.q2, i1, 0, 0, 0);
-        const f16acc i2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(rows.q1, cols.q1, zacc, 0, 0, 0);
-        const f16acc rs = __builtin_amdgcn_mfma_f32_32x32x16_f16(rows.q2, cols.q2, zacc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float alt = i2[r] + rs[r];
-            if (!(fabsf(alt - ch[r]) <= 1e-2f + 1e-4f * fabsf(alt))) {
-                const unsigned slot = atomicAdd(&g_emd_dbg_n, 1u);
-                if (slot < 16) {
-                    g_emd_dbg[slot * 8 + 0] = ch[r]; g_emd_dbg[slot * 8 + 1] = alt; g_emd_dbg[slot * 8 + 2] = i2[r]; g_emd_dbg[slot * 8 + 3] = rs[r];
-                    g_emd_dbg[slot * 8 + 4] = (float)threadIdx.x; g_emd_dbg[slot * 8 + 5] = (float)r;
-                    g_emd_dbg[slot * 8 + 6] = (float)blockIdx.x; g_emd_dbg[slot * 8 + 7] = (float)blockIdx.y;
-                }
-            }
-        }
-        return ch;
-    }
-#elif EMD_DBG & 2
-    f16acc ints = __builtin_amdgcn_mfma_f32_32x32x16_f16(rows.q1, cols.q1, zacc, 0, 0, 0);
-    f16acc rest = __builtin_amdgcn_mfma_f32_32x32x16_f16(rows.q2, cols.q2, zacc, 0, 0, 0);
-    return ints + rest;
-#else
     const f16acc ints = __builtin_amdgcn_mfma_f32_32x32x16_f16(rows.q1, cols.q1, zacc, 0, 0, 0);
-    f16acc acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(rows.q2, cols.q2, ints, 0, 0, 0);
-#if EMD_DBG & 1
-    asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" : "+v"(acc));
-#endif
-#if EMD_DBG & 4
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-    return acc;
-#endif
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(rows.q2, cols.q2, ints, 0, 0, 0);
 }
 
-// EMD_PIN_LOADS=1 (an A/B build, off by default): keep every prefetch behind the VALU instructions that consumed the previous
-// tile's MFMA results, and every tile's MFMAs behind the prefetch in front of it.  Built in r06 to test ONE hypothesis for r05's
-// run-to-run differences -- the compiler counts a register dead once its last reader has issued and hands a scaled fragment's
-// registers to the next prefetch ("v_mfma ... v[122:125] ...; global_load_dwordx4 v[122:125]" behind four queued MFMAs);
-// tools/mfma_overlap_check.py --war lists such sites.  REJECTED: tools/ubench/mfma_war.hip and mfma_valu_war.hip overwrite the
-// sources of up to seven queued MFMAs by a cache-resident load / by VALU writes in the very next slot, 1.6e7 times at up to four
-// waves per SIMD, without one wrong result -- the hardware interlocks it; the pinned build flickered like the unpinned one, and
-// both repeat once the vectoriser is off (what the vectoriser wrote was "v_pk_fma_f32 ... op_sel:[0,1,0]", a packed form
-// that loses its low half in lanes 48-63 beside another wave's MFMAs -- tools/ubench/pk_vs_mfma_forms.hip).  The pins cost nothing
-// measurable (cfg5 2.740 vs 2.741 ms).
-#ifndef EMD_PIN_LOADS
-#define EMD_PIN_LOADS 0
-#endif
-// ... and the MFMAs of the tile that follows a prefetch must not be moved IN FRONT of it (an MFMA is no memory operation: the
-// scheduler hoists it over a plain memory barrier): the tile's raw fragments pass through the barrier
-__device__ __forceinline__ void mfmas_stay_behind(u4 &r) {
-#if EMD_PIN_LOADS
-    asm volatile("" : "+v"(r) : : "memory");
-#else
-    asm volatile("" ::: "memory");
-#endif
-}
-template <int N>
-__device__ __forceinline__ void loads_stay_behind(float (&v)[N]) {
-#if EMD_PIN_LOADS
+// Between a prefetch and the arithmetic of the tile that follows it: a compiler memory barrier, so that the next tile's loads are
+// issued in front of this tile's work and none of them sinks into it.  (An MFMA is no memory operation; the form that also passed
+// the raw fragments through the barrier to pin the MFMAs was EMD_PIN_LOADS -- rejected, no difference: DESIGN 4.6.)
+// REGS: the raw fragment registers (u4) of the tile -- one barrier for each, as the measured and gated listing has them: the
+// scheduler ends a region at every one, and another count allocates the registers of emd_mfma_rows_kernel<1> and
+// emd_mfma_grad_kernel differently.
+template <int REGS>
+__device__ __forceinline__ void mfmas_stay_behind() {
 #pragma unroll
-    for (int i = 0; i < N; ++i) asm volatile("" : "+v"(v[i]) : : "memory");
-#endif
+    for (int u = 0; u < REGS; ++u) asm volatile("" ::: "memory");
 }
 
 // Passes over cloud 1's points (columns; cloud 2's LIVE points stream past as row tiles with their weights):
@@ -814,15 +756,13 @@ __global__ __launch_bounds__(64 * MSL) void emd_mfma_cols_kernel(MfmaState st, i
             afB[0] = candrec[(size_t)n1 * TQ]; afB[1] = candrec[(size_t)n1 * TQ + 2];
 #pragma unroll
             for (int i = 0; i < 4; ++i) waB[i] = *(const float4 *)(w0 + n1 * 32 + 8 * i);
-            mfmas_stay_behind(afA[0]); mfmas_stay_behind(afA[1]);
+            mfmas_stay_behind<2>();
             tile(afA, waA);
-            loads_stay_behind(sa);
             afA[0] = candrec[(size_t)n2 * TQ]; afA[1] = candrec[(size_t)n2 * TQ + 2];
 #pragma unroll
             for (int i = 0; i < 4; ++i) waA[i] = *(const float4 *)(w0 + n2 * 32 + 8 * i);
-            mfmas_stay_behind(afB[0]); mfmas_stay_behind(afB[1]);
+            mfmas_stay_behind<2>();
             if (ct + 1 < te) tile(afB, waB);
-            loads_stay_behind(sa);
         }
     }
 #pragma unroll
@@ -932,28 +872,14 @@ __global__ __launch_bounds__(64 * MSL) void emd_mfma_rows_kernel(MfmaState st, i
                 }
             }
         };
-        auto fence = [&](u4 (&bfr)[NB][2]) {
-#pragma unroll
-            for (int u = 0; u < NB; ++u) { mfmas_stay_behind(bfr[u][0]); mfmas_stay_behind(bfr[u][1]); }
-        };
-        auto pin = [&]() {                       // (one sum per row tile: each depends on that tile's last MFMA)
-            float last[RT];
-#pragma unroll
-            for (int t = 0; t < RT; ++t) last[t] = s[t][15];
-            loads_stay_behind(last);
-#pragma unroll
-            for (int t = 0; t < RT; ++t) s[t][15] = last[t];
-        };
         load(tb, bfA, wA);
         for (int ct = tb; ct < te; ct += 2 * NB) {
             load(ct + NB, bfB, wB);
-            fence(bfA);
+            mfmas_stay_behind<2 * NB>();
             tiles_of(bfA, wA);
-            pin();
             load(ct + 2 * NB, bfA, wA);
-            fence(bfB);
+            mfmas_stay_behind<2 * NB>();
             if (ct + NB < te) tiles_of(bfB, wB);
-            pin();
         }
     }
 #pragma unroll
@@ -1083,16 +1009,9 @@ struct LevelScales { LevelFac lf[NLEVEL]; };
 // Measured (cfg5, 16 x 8192^2): 1.18 ms = `match` written at 3.6 TB/s; MTM = 4 (512 contiguous bytes per row and wave) and the
 // unmasked store path moved it by < 10 %: it is the write that bounds it, not the instruction count.
 constexpr int MTM = 2;
-#ifndef EMD_NT_STORE
-#define EMD_NT_STORE 1
-#endif
-#if EMD_NT_STORE
 // `match` (4 n m bytes: 4.3 GB at cfg5) is written once and not read again by the call: a streaming store.  r06, measured at cfg5
 // (B = 16, N = 8192): emd_mfma_materialize_kernel 1.31 -> 0.82 ms, the approxmatch + cost call 2.73 -> 2.24 ms
 #define EMD_MATCH_STORE(v, p) __builtin_nontemporal_store((v), (p))
-#else
-#define EMD_MATCH_STORE(v, p) (*(p) = (v))
-#endif
 // The matching's entries of ONE 32-row tile ct of `order` against a wave's MTM column tiles, the levels in order: mm[t][r] in the
 // accumulators' layout (register 4 i + jj of lane (half, col): row ct 32 + 8 i + 4 half + jj, column tile t).  Shared by the
 // materialising kernel and the recomputing gradient kernel (emd_mfma_grad_kernel): what the gradient rebuilds are these bits.
@@ -1116,22 +1035,21 @@ __device__ __forceinline__ void mfma_match_tile(int ct, int bi, int nb, int MP, 
         float rlj[MTM];
 #pragma unroll
         for (int t = 0; t < MTM; ++t) rlj[t] = rl_w[j][t * 32 + col];
-        // every load of this level is issued in front of its first MFMA (the raw row fragment passes through the barrier
-        // the MFMAs' operands are made behind), none before its last MFMA has been consumed (below): mfmas_stay_behind
-        u4 afj[2] = {af[0], af[1]};
-        mfmas_stay_behind(afj[0]); mfmas_stay_behind(afj[1]);
-        const Frag as = scale_frag(afj[0], afj[1], svr);
+        // every load of this level is issued in front of its first MFMA: mfmas_stay_behind
+        mfmas_stay_behind<2>();
+        const Frag as = scale_frag(af[0], af[1], svr);
 #pragma unroll
         for (int t = 0; t < MTM; ++t) {
             const f16acc acc = pair_exponents(as, scale_frag(bfraw[t][0], bfraw[t][1], svc), zacc);
 #pragma unroll
             for (int r = 0; r < 16; ++r) mm[t][r] = __builtin_fmaf(fmul(fast_exp2(acc[r]), rlj[t]), pick4(rr, r), mm[t][r]);
         }
-        {   // the next level's loads stay behind this level's MFMAs (loads_stay_behind)
+        {   // No operation -- what is left of the EMD_PIN_LOADS fence that stood here.  It stays until the next change that
+            // regenerates the device listing anyway: without it emd_mfma_grad_kernel (alone) comes out with two fragment register
+            // quads exchanged, and this file's device code is held identical to the measured one.
             float last[MTM];
 #pragma unroll
             for (int t = 0; t < MTM; ++t) last[t] = mm[t][15];
-            loads_stay_behind(last);
 #pragma unroll
             for (int t = 0; t < MTM; ++t) mm[t][15] = last[t];
         }
@@ -1139,9 +1057,9 @@ __device__ __forceinline__ void mfma_match_tile(int ct, int bi, int nb, int MP, 
 }
 
 template <bool COST, bool STORE>
-// (no __restrict__ on what the loop loads: a load from memory the compiler knows nobody writes may cross the asm barriers that
-// keep loads and MFMAs apart -- loads_stay_behind / mfmas_stay_behind -- and r06's first build sank the last ratioR load of a
-// level behind that level's MFMAs, into the registers of a fragment they read)
+// (no __restrict__ on what the loop loads: a load from memory the compiler knows nobody writes may cross the asm barrier that
+// keeps loads and MFMAs apart -- mfmas_stay_behind -- and r06's first build sank the last ratioR load of a level behind that
+// level's MFMAs, into the registers of a fragment they read)
 __global__ __launch_bounds__(64 * MSL) void emd_mfma_materialize_kernel(MfmaState st, LevelScales ls, const float *xyz1,
                                                                         const float *ws, size_t lstride,
                                                                         const u4 *recA_s, const float *rr_s,
@@ -1781,35 +1699,76 @@ int pick_slices(int b, int npoints, int ninner) {
 
 }  // namespace
 
-// bytes of the deferred path's own regions (ratio slots, packed-VALU records, materialisation records, cost partials)
-static size_t deferred_bytes(int b, int n, int m) {
-    // NLEVEL ratio slots | 16 B alignment slack | (x,y,z,w) records of the passes | 12-float records of the materialisation
-    return (size_t)b * NLEVEL * ((size_t)n + m) * sizeof(float) + 16 + (size_t)b * ((size_t)n + 2 * (size_t)m) * sizeof(float4) +
-           (size_t)b * m * 12 * sizeof(float) + (size_t)b * ((n + PPW - 1) / PPW) * MAXS * sizeof(float);
-}
-// ... and of the matrix-core passes behind them (MfmaRegions below lays them out; every region 64-byte aligned)
-struct MfmaRegions {
-    size_t flag, meta, count, counts, recB1, recA2d, recA2[2], idx2[2], remR[2], ratioR, ratioL, order, recAs, rrs, c2s, ls, end;
+// ---- the host side ----------------------------------------------------------------------------------------------------------
+// The approx-EMD workspace, laid out in ONE place: every region as a byte offset from the workspace pointer, and the total.
+//   ratio slots [NLEVEL][pair][ratioL (n) | ratioR (m)]  (at 0)  | up to 16 B of slack
+//   pk        float4 [pair][C1 (n) | C2a (m) | C2b (m)]: the packed-VALU passes' records
+//   rec       float [pair][m][12]: the packed-VALU materialisation's records
+//   costpart  float [pair][cstride]: both families' cost partials                                   | up to 64 B of slack
+//   flag ... ls: the matrix-core passes' regions, every one 64-byte aligned and padded
+// pk and flag are aligned as ADDRESSES (16 / 64 bytes), so the offsets behind them depend on the workspace pointer `base`; the
+// total counts both slacks in full and does not (sizes are asked with base 0).  Public: include/dpf_hip.h (the saved state of
+// dpf_matchcostgrad_recompute_ws); tests/test_host_cpu.py pins the totals.
+struct EmdLayout {
+    int NP, MP;                          // the clouds' sizes padded to the matrix-core passes' MPW points
+    int cstride;                         // cost partials per pair
+    size_t rstride, lstride, pstride;    // a ratio slot's floats per pair and per level; pk's records per pair
+    size_t pk, rec, costpart;
+    size_t flag, meta, count, counts, recB1, recA2d, recA2[2], idx2[2], remR[2], ratioR, ratioL, order, recAs, rrs, c2s, ls;
+    size_t total;
 };
-static MfmaRegions mfma_regions(int b, int n, int m) {
-    const size_t NP = (size_t)(n + MPW - 1) / MPW * MPW, MP = (size_t)(m + MPW - 1) / MPW * MPW, B = (size_t)b;
-    MfmaRegions r;
-    size_t at = 0;
+static EmdLayout emd_layout(int b, int n, int m, uintptr_t base = 0) {
+    EmdLayout L;
+    const size_t B = (size_t)b;
+    auto padded = [](int v) { return round_up(v, MPW); };
+    L.NP = padded(n); L.MP = padded(m);
+    L.cstride = (n + PPW - 1) / PPW * MAXS;
+    L.rstride = (size_t)n + m; L.lstride = B * L.rstride; L.pstride = (size_t)n + 2 * (size_t)m;
+    const size_t slots = NLEVEL * L.lstride * sizeof(float);
+    L.pk = ((base + slots + 15) & ~(uintptr_t)15) - base;
+    L.rec = L.pk + B * L.pstride * sizeof(float4);
+    L.costpart = L.rec + B * m * 12 * sizeof(float);
+    const size_t deferred = slots + 16 + (L.costpart - L.pk) + B * L.cstride * sizeof(float);     // with the 16 B in full
+    const size_t mbase = ((base + deferred + 63) & ~(uintptr_t)63) - base;
+    size_t at = mbase;
     auto take = [&](size_t bytes) { const size_t here = at; at += (bytes + 63) & ~(size_t)63; return here; };
-    constexpr size_t RB = 16 * RECQ;                                             // bytes of a point record
-    r.flag = take(16); r.meta = take(B * METAF * 4); r.count = take(B * 4); r.counts = take(NLEVEL * B * 4);
-    r.recB1 = take(B * NP * RB); r.recA2d = take(B * MP * RB);
-    for (int u = 0; u < 2; ++u) { r.recA2[u] = take(B * MP * RB); r.idx2[u] = take(B * MP * 4); r.remR[u] = take(B * MP * 4); }
-    r.ratioR = take(B * MP * 4); r.ratioL = take(B * NP * 4); r.order = take(B * MP * 4);
-    r.recAs = take(B * MP * RB); r.rrs = take(NLEVEL * B * MP * 4); r.c2s = take(3 * B * MP * 4); r.ls = take(B * MP * 4);
-    r.end = at;
-    return r;
+    const size_t NP = (size_t)L.NP, MP = (size_t)L.MP, RB = 16 * RECQ;           // RB: bytes of a point record
+    L.flag = take(16); L.meta = take(B * METAF * 4); L.count = take(B * 4); L.counts = take(NLEVEL * B * 4);
+    L.recB1 = take(B * NP * RB); L.recA2d = take(B * MP * RB);
+    for (int u = 0; u < 2; ++u) { L.recA2[u] = take(B * MP * RB); L.idx2[u] = take(B * MP * 4); L.remR[u] = take(B * MP * 4); }
+    L.ratioR = take(B * MP * 4); L.ratioL = take(B * NP * 4); L.order = take(B * MP * 4);
+    L.recAs = take(B * MP * RB); L.rrs = take(NLEVEL * B * MP * 4); L.c2s = take(3 * B * MP * 4); L.ls = take(B * MP * 4);
+    L.total = deferred + 64 + (at - mbase);                                                      // with the 64 B in full
+    return L;
 }
-static size_t mfma_bytes(int b, int n, int m) { return 64 + mfma_regions(b, n, m).end; }
+template <class T>
+static T *ws_at(const void *workspace, size_t offset) { return (T *)((uint8_t *)workspace + offset); }
+
+// The matrix-core kernels' view of a workspace (a call site that does not use a field gets it all the same: plain pointers into
+// memory the caller owns)
+static MfmaState mfma_state(const EmdLayout &L, const void *ws, int b, int n, int m, float *temp, const unsigned *gate, PairMap pm) {
+    MfmaState st{};
+    st.n = n; st.m = m; st.NP = L.NP; st.MP = L.MP; st.nb = b;
+    st.recB1 = ws_at<const u4>(ws, L.recB1);
+    for (int u = 0; u < 2; ++u) {
+        st.recA2[u] = ws_at<u4>(ws, L.recA2[u]); st.idx2[u] = ws_at<int>(ws, L.idx2[u]); st.remainR_c[u] = ws_at<float>(ws, L.remR[u]);
+    }
+    st.ratioR_c = ws_at<float>(ws, L.ratioR); st.ratioL_p = ws_at<float>(ws, L.ratioL);
+    st.count = ws_at<int>(ws, L.count); st.counts = ws_at<int>(ws, L.counts); st.order = ws_at<int>(ws, L.order);
+    st.temp = temp; st.rstride = L.rstride; st.gate = gate; st.pm = pm;
+    return st;
+}
 
 extern "C" size_t dpf_approxmatch_workspace_bytes(int b, int n, int m) {
     if (b <= 0 || n <= 0 || m <= 0) return 0;
-    return deferred_bytes(b, n, m) + mfma_bytes(b, n, m);
+    return emd_layout(b, n, m).total;
+}
+
+// The entries' common prologue, in this order: sizes, the empty batch, the pointers, the grid's limit (the batch is grid y).
+// True: the call is over, `rc` is what it returns.
+static bool args_settle(int &rc, long b, int n, int m, bool pointers) {
+    rc = (b < 0 || n <= 0 || m <= 0) ? DPF_EINVAL : b == 0 ? 0 : !pointers ? DPF_EINVAL : b > 65535 ? DPF_ENOSUP : 1;
+    return rc != 1;
 }
 
 // 1 (default): the deferred path's passes run on the matrix cores when the coordinates allow it; 0: always the packed-VALU
@@ -1826,6 +1785,11 @@ static LevelFac level_fac(int j) {
     auto h16 = [](int e) { return (unsigned)((e + 15) << 10); };            // bits of the fp16 number 2^e, -14 <= e <= 15
     const int e = 2 * (j - 7), eF = e < -14 ? -14 : e;
     return LevelFac{h16(eF), h16(e - eF), h16(j - 7)};
+}
+static LevelScales level_scales() {
+    LevelScales ls;
+    for (int lj = 0; lj < NLEVEL; ++lj) ls.lf[lj] = level_fac(7 - lj);
+    return ls;
 }
 static float level_lvl2(int j) {
     const float level = -powf(4.0f, (float)j);
@@ -1854,11 +1818,10 @@ struct PairCall { PairMap pm; unsigned *gates; int slice_b; };
 static int approxmatch_impl(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *temp, float *cost,
                             void *workspace, size_t workspace_bytes, dpf_stream_t stream, const PairCall *pc = nullptr,
                             bool keep_state = false) {
-    if (b < 0 || n <= 0 || m <= 0) return DPF_EINVAL;
-    if (b == 0) return 0;
-    if (!xyz1 || !xyz2 || !temp || (!match && !pc && !keep_state)) return DPF_EINVAL;
-    if (b > 65535) return DPF_ENOSUP;
-    const bool deferred = workspace != nullptr && workspace_bytes >= dpf_approxmatch_workspace_bytes(b, n, m);
+    int rc;
+    if (args_settle(rc, b, n, m, xyz1 && xyz2 && temp && (match || pc || keep_state))) return rc;
+    const EmdLayout L = emd_layout(b, n, m, (uintptr_t)workspace);
+    const bool deferred = workspace != nullptr && workspace_bytes >= L.total;
     if ((pc || keep_state) && (!deferred || !cost)) return DPF_EINVAL;
     const PairMap pm = pc ? pc->pm : PairMap{1, b, 0};
     const int sb = pc ? pc->slice_b : b;
@@ -1868,24 +1831,25 @@ static int approxmatch_impl(int b, int n, int m, const float *xyz1, const float 
     else        { multiL = (float)(m / n); multiR = 1; }
     static const bool env_matrix = [] { const char *e = getenv("DPF_EMD_MATRIX"); return !(e && e[0] == '0'); }();
     const bool matrix = deferred && g_matrix_path && env_matrix;
-    // regions of the matrix-core passes (behind the deferred path's own)
-    const int NP = (n + MPW - 1) / MPW * MPW, MP = (m + MPW - 1) / MPW * MPW;
-    uint8_t *mbase = deferred ? (uint8_t *)(((uintptr_t)workspace + deferred_bytes(b, n, m) + 63) & ~(uintptr_t)63) : nullptr;
-    const MfmaRegions mr = mfma_regions(b, n, m);
-    unsigned *flag = matrix ? (pc ? pc->gates : (unsigned *)(mbase + mr.flag)) : nullptr;
-    float *meta = (float *)(mbase + mr.meta);
+    unsigned *flag = matrix ? (pc ? pc->gates : ws_at<unsigned>(workspace, L.flag)) : nullptr;
     hipLaunchKernelGGL(emd_init_kernel, dim3((n + m + 255) / 256, b), dim3(256), 0, s, n, m, multiL, multiR, temp, flag, pm);
     const int s1 = pick_match_slices(sb, n, m), s2 = pick_match_slices(sb, m, n);
     const dim3 g1((n + 63) / 64, b), g2((m + 63) / 64, b);
     const dim3 h1((n + PPW - 1) / PPW, b), h2((m + PPW - 1) / PPW, b);               // deferred kernels: 128 points per wave
-    const size_t rstride = deferred ? (size_t)(n + m) : (size_t)(n + m) * 2;     // per-cloud stride of a ratio slot
-    const size_t lstride = (size_t)b * (n + m);                                   // per-level stride in the workspace
-    // packed records of the deferred path, after the NLEVEL ratio slots
-    const size_t pstride = (size_t)n + 2 * (size_t)m;
-    float4 *pk = deferred ? (float4 *)(((uintptr_t)((float *)workspace + NLEVEL * lstride) + 15) & ~(uintptr_t)15) : nullptr;
-    float *rec = deferred ? (float *)(pk + (size_t)b * pstride) : nullptr;
+    // a ratio slot: a level's of the workspace, or (read-modify-write) the one behind remainL | remainR in every cloud's `temp`
+    const size_t rstride = deferred ? L.rstride : 2 * L.rstride, lstride = L.lstride, pstride = L.pstride;
+    float *ws = (float *)workspace;
+    float4 *pk = deferred ? ws_at<float4>(workspace, L.pk) : nullptr;
+    float *rec = deferred ? ws_at<float>(workspace, L.rec) : nullptr;
+    // The cost partials of a cloud pair: ONE region and stride for both families.  With a verdict per pair (dpf_pairwise_emd)
+    // pairs of both families share a launch, and strides of their own -- (NP / 64) m1 and ceil(n / 128) s1, 128 and 64 at 2 048
+    // points -- would lay one pair's partials over another's.
+    static_assert(MPW == PPW && MPW / (32 * MTM) * MSL <= MAXS, "matrix-core cost partials exceed the per-pair region");
+    float *costpart = deferred ? ws_at<float>(workspace, L.costpart) : nullptr;
+    const int cstride = L.cstride;
     // (the range check first: every kernel of either family looks at its verdict)
-    if (matrix) hipLaunchKernelGGL(emd_mfma_prep_kernel, dim3(b), dim3(1024), 0, s, n, m, xyz1, xyz2, meta, flag, pm);
+    if (matrix)
+        hipLaunchKernelGGL(emd_mfma_prep_kernel, dim3(b), dim3(1024), 0, s, n, m, xyz1, xyz2, ws_at<float>(workspace, L.meta), flag, pm);
     // (r06, VERDICT r05 #4: the family that is not wanted was moved to a forked side stream -- built, parity-green, measured at
     // cfg5: 2.7323 ms against 2.7315 ms with everything on the caller's stream.  The 31 gated launches sit at the END of the
     // call's sequence, back to back, and their launch latencies overlap each other; r05's "0.13 ms of empty launches" was the
@@ -1894,89 +1858,57 @@ static int approxmatch_impl(int b, int n, int m, const float *xyz1, const float 
         hipLaunchKernelGGL(emd_pack_init_kernel, dim3((m + 255) / 256, b), dim3(256), 0, s, m, multiR, xyz2, pk + n, pstride,
                            (const unsigned *)flag, pm);
     int mfma_cost_parts = 0;
-    // The cost partials of a cloud pair: ONE stride for both families, the region's capacity per pair (deferred_bytes).  With a
-    // verdict per pair (dpf_pairwise_emd) pairs of both families share a launch, and strides of their own -- (NP / 64) m1 and
-    // ceil(n / 128) s1, 128 and 64 at 2 048 points -- would lay one pair's partials over another's.
-    static_assert(MPW == PPW && MPW / (32 * MTM) * MSL <= MAXS, "matrix-core cost partials exceed the per-pair region");
-    const int cstride = (n + PPW - 1) / PPW * MAXS;
     if (matrix) {
         // the matrix-core family: gate 0.  Per level: pass 1, pass 2, pass 3 over the live list, then its compaction
-        // debug (tests/diag/emd_bisect.py): DPF_EMD_STOP_AFTER=k returns behind the k-th launch of this family
-        const char *stop_env = getenv("DPF_EMD_STOP_AFTER");
-        int stop_left = stop_env ? atoi(stop_env) : -1;
-#define EMD_STOP_CHECK() do { if (stop_left > 0 && --stop_left == 0) return (int)hipGetLastError(); } while (0)
-        MfmaState st{};
-        st.n = n; st.m = m; st.NP = NP; st.MP = MP; st.nb = b;
-        st.recB1 = (const u4 *)(mbase + mr.recB1);
-        for (int u = 0; u < 2; ++u) {
-            st.recA2[u] = (u4 *)(mbase + mr.recA2[u]); st.idx2[u] = (int *)(mbase + mr.idx2[u]); st.remainR_c[u] = (float *)(mbase + mr.remR[u]);
-        }
-        st.ratioR_c = (float *)(mbase + mr.ratioR); st.ratioL_p = (float *)(mbase + mr.ratioL);
-        st.count = (int *)(mbase + mr.count); st.counts = (int *)(mbase + mr.counts); st.order = (int *)(mbase + mr.order);
-        st.temp = temp; st.rstride = rstride; st.gate = flag; st.pm = pm;
-        u4 *recA2_dense = (u4 *)(mbase + mr.recA2d), *recA_s = (u4 *)(mbase + mr.recAs);
-        float *rr_s = (float *)(mbase + mr.rrs), *c2soa_s = (float *)(mbase + mr.c2s);
-        int *l_s = (int *)(mbase + mr.ls);
-        float *ws = (float *)workspace;
+        const int NP = L.NP, MP = L.MP;
+        const MfmaState st = mfma_state(L, workspace, b, n, m, temp, flag, pm);
+        u4 *recA2_dense = ws_at<u4>(workspace, L.recA2d), *recA_s = ws_at<u4>(workspace, L.recAs);
+        float *rr_s = ws_at<float>(workspace, L.rrs), *c2soa_s = ws_at<float>(workspace, L.c2s);
+        int *l_s = ws_at<int>(workspace, L.ls);
         hipLaunchKernelGGL(emd_mfma_pack_kernel, dim3((NP + MP + 255) / 256, b), dim3(256), 0, s, st, multiR, xyz1, xyz2,
-                           (const float *)meta, recA2_dense, ws, lstride);
-        EMD_STOP_CHECK();
+                           ws_at<const float>(workspace, L.meta), recA2_dense, ws, lstride);
         const int m1 = pick_mfma_slices(sb, n, m), m2 = pick_mfma_slices(sb, m, n);
         const dim3 q1(NP / MPW, b), q2(MP / MPW, b);
-        LevelScales ls;
         int cur = 0, lj = 0;
         for (int j = 7; j > -2; --j, ++lj) {
             float *rb = ws + lj * lstride;
-            ls.lf[lj] = level_fac(j);
             hipLaunchKernelGGL(emd_mfma_cols_kernel<0>, q1, dim3(64, m1), 0, s, st, cur, level_fac(j), rb);
-        EMD_STOP_CHECK();
             if (j == 7) {
                 hipLaunchKernelGGL(emd_mfma_rows_kernel<4>, q2, dim3(64, m2), 0, s, st, cur, level_fac(j), rb, 0);
-                EMD_STOP_CHECK();
             } else {
                 // (r06: both regimes as ONE launch -- every fourth workgroup of the sparse regime's grid taking four tiles in the
                 // dense one -- was built and measured: cfg5 2.73 -> 3.53 ms.  The two launches stay; the one whose regime it is
                 // not costs 5-7 us)
                 hipLaunchKernelGGL(emd_mfma_rows_kernel<4>, q2, dim3(64, m2), 0, s, st, cur, level_fac(j), rb, 1);
-                EMD_STOP_CHECK();
                 hipLaunchKernelGGL(emd_mfma_rows_kernel<1>, dim3(MP / 32, b), dim3(64, MSL), 0, s, st, cur, level_fac(j), rb, 2);
-                EMD_STOP_CHECK();
             }
             hipLaunchKernelGGL(emd_mfma_cols_kernel<3>, q1, dim3(64, m1), 0, s, st, cur, level_fac(j), rb);
-        EMD_STOP_CHECK();
             if (j > -1) {
                 hipLaunchKernelGGL(emd_mfma_compact_kernel<false>, dim3(b), dim3(1024), 0, s, st, cur, lj);
-        EMD_STOP_CHECK();
                 cur ^= 1;
             } else {
                 hipLaunchKernelGGL(emd_mfma_compact_kernel<true>, dim3(b), dim3(1024), 0, s, st, cur, lj);
-        EMD_STOP_CHECK();
             }
         }
         hipLaunchKernelGGL(emd_mfma_gather_kernel, dim3((MP + 255) / 256, b), dim3(256), 0, s, st, (const u4 *)recA2_dense, xyz2,
                            (const float *)ws, lstride, recA_s, rr_s, c2soa_s, l_s);
-        EMD_STOP_CHECK();
         const dim3 qm(NP / (32 * MTM), b);
-        float *costpart_m = rec + (size_t)b * m * 12;
-        if (!match)
-            hipLaunchKernelGGL((emd_mfma_materialize_kernel<true, false>), qm, dim3(64, m1), 0, s, st, ls, xyz1, (const float *)ws,
-                               lstride, (const u4 *)recA_s, (const float *)rr_s, (const float *)c2soa_s, (const int *)l_s, match,
-                               costpart_m, cstride);
-        else if (cost)
-            hipLaunchKernelGGL((emd_mfma_materialize_kernel<true, true>), qm, dim3(64, m1), 0, s, st, ls, xyz1, (const float *)ws,
-                               lstride, (const u4 *)recA_s, (const float *)rr_s, (const float *)c2soa_s, (const int *)l_s, match,
-                               costpart_m, cstride);
-        else
-            hipLaunchKernelGGL((emd_mfma_materialize_kernel<false, true>), qm, dim3(64, m1), 0, s, st, ls, xyz1, (const float *)ws,
-                               lstride, (const u4 *)recA_s, (const float *)rr_s, (const float *)c2soa_s, (const int *)l_s, match,
-                               costpart_m, cstride);
+        // its <COST, STORE> form: no matching -> the sums alone (a cost is asked for then, above), else a matching with or without
+        // them.  (Here and below, in this order: the templates' kernels stand in the object in the order they are first named.)
+        const auto materialize = [&] {
+            if (!match) return emd_mfma_materialize_kernel<true, false>;
+            if (cost) return emd_mfma_materialize_kernel<true, true>;
+            return emd_mfma_materialize_kernel<false, true>;
+        }();
+        hipLaunchKernelGGL(materialize, qm, dim3(64, m1), 0, s, st, level_scales(), xyz1,
+                           (const float *)ws, lstride, (const u4 *)recA_s, (const float *)rr_s, (const float *)c2soa_s,
+                           (const int *)l_s, match, costpart, cstride);
         mfma_cost_parts = (int)qm.x * m1;
-#undef EMD_STOP_CHECK
     }
     int li = 0;
     for (int j = 7; j > -2; --j, ++li) {                    // approxmatch.cu:24 (the j==-2 branch is dead)
         const float lvl2 = level_lvl2(j);
-        float *rb = deferred ? (float *)workspace + li * lstride : temp + (size_t)(n + m);
+        float *rb = deferred ? ws + li * lstride : temp + (size_t)(n + m);
         if (deferred) {
             // the packed-VALU family: gate 1 (always when the matrix path is off: flag == nullptr)
             hipLaunchKernelGGL(emd_ratio2_kernel<1>, h1, dim3(64, s1), 0, s, n, m, lvl2, xyz1, xyz2, temp, rb, rstride, pk, pstride,
@@ -1995,28 +1927,24 @@ static int approxmatch_impl(int b, int n, int m, const float *xyz1, const float 
             hipLaunchKernelGGL(emd_match_kernel<1>, g1, dim3(64, s1), 0, s, n, m, lvl2, xyz1, xyz2, match, temp, rb, rstride);
     }
     if (deferred) {
-        const LevelPairs lp = level_pairs();
         hipLaunchKernelGGL(emd_pack_levels_kernel, dim3((m + 255) / 256, b), dim3(256), 0, s, n, m, xyz2,
-                           (const float *)workspace, lstride, rstride, rec, (const unsigned *)flag, pm);
-        float *costpart = rec + (size_t)b * m * 12;
+                           (const float *)ws, lstride, rstride, rec, (const unsigned *)flag, pm);
+        const auto materialize2 = [&] {
+            if (cost && match) return emd_materialize2_kernel<true, true>;
+            if (cost) return emd_materialize2_kernel<true, false>;
+            return emd_materialize2_kernel<false, true>;
+        }();
+        hipLaunchKernelGGL(materialize2, h1, dim3(64, s1), 0, s, n, m, level_pairs(), xyz1,
+                           (const float *)rec, match, (const float *)ws, lstride, rstride, costpart, cstride, (const unsigned *)flag, pm);
         if (cost) {
-            if (match)
-                hipLaunchKernelGGL((emd_materialize2_kernel<true, true>), h1, dim3(64, s1), 0, s, n, m, lp, xyz1, (const float *)rec,
-                                   match, (const float *)workspace, lstride, rstride, costpart, cstride, (const unsigned *)flag, pm);
-            else
-                hipLaunchKernelGGL((emd_materialize2_kernel<true, false>), h1, dim3(64, s1), 0, s, n, m, lp, xyz1, (const float *)rec,
-                                   match, (const float *)workspace, lstride, rstride, costpart, cstride, (const unsigned *)flag, pm);
             hipLaunchKernelGGL(emd_cost_sum_kernel, dim3(b), dim3(256), 0, s, (int)h1.x * s1, cstride, (const float *)costpart, cost,
                                (const unsigned *)flag, 1u, pm);
             if (matrix)
                 hipLaunchKernelGGL(emd_cost_sum_kernel, dim3(b), dim3(256), 0, s, mfma_cost_parts, cstride, (const float *)costpart,
                                    cost, (const unsigned *)flag, 0u, pm);
-        } else {
-            hipLaunchKernelGGL((emd_materialize2_kernel<false, true>), h1, dim3(64, s1), 0, s, n, m, lp, xyz1, (const float *)rec,
-                               match, (const float *)workspace, lstride, rstride, costpart, cstride, (const unsigned *)flag, pm);
         }
         if (keep_state)
-            hipLaunchKernelGGL(emd_save_setting_kernel, dim3(1), dim3(64), 0, s, (unsigned *)(mbase + mr.flag), matrix ? 1u : 0u);
+            hipLaunchKernelGGL(emd_save_setting_kernel, dim3(1), dim3(64), 0, s, ws_at<unsigned>(workspace, L.flag), matrix ? 1u : 0u);
     }
     return (int)hipGetLastError();
 }
@@ -2028,31 +1956,20 @@ extern "C" int dpf_debug_emd_exponents(int n, int m, const float *xyz1, const fl
                                        void *workspace, size_t workspace_bytes, dpf_stream_t stream) {
     static const unsigned slot_mask = [] { const char *e = getenv("DPF_EMD_DEBUG_SLOTS"); return e ? (unsigned)strtoul(e, nullptr, 0) : ~0u; }();
     if (n <= 0 || m <= 0 || level_j < -1 || level_j > 7 || !xyz1 || !xyz2 || !out) return DPF_EINVAL;
-    if (!workspace || workspace_bytes < dpf_approxmatch_workspace_bytes(1, n, m)) return DPF_EINVAL;
+    const EmdLayout L = emd_layout(1, n, m, (uintptr_t)workspace);
+    if (!workspace || workspace_bytes < L.total) return DPF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    const int NP = (n + MPW - 1) / MPW * MPW, MP = (m + MPW - 1) / MPW * MPW;
-    uint8_t *mbase = (uint8_t *)(((uintptr_t)workspace + deferred_bytes(1, n, m) + 63) & ~(uintptr_t)63);
-    const MfmaRegions mr = mfma_regions(1, n, m);
-    unsigned *flag = (unsigned *)(mbase + mr.flag);
-    float *meta = (float *)(mbase + mr.meta);
+    unsigned *flag = ws_at<unsigned>(workspace, L.flag);
+    float *meta = ws_at<float>(workspace, L.meta);
     hipError_t e = dpf_zero_async(flag, 16, s);
     if (e != hipSuccess) return (int)e;
-    MfmaState st{};
-    st.n = n; st.m = m; st.NP = NP; st.MP = MP; st.nb = 1;
-    st.recB1 = (const u4 *)(mbase + mr.recB1);
-    for (int u = 0; u < 2; ++u) {
-        st.recA2[u] = (u4 *)(mbase + mr.recA2[u]); st.idx2[u] = (int *)(mbase + mr.idx2[u]); st.remainR_c[u] = (float *)(mbase + mr.remR[u]);
-    }
-    st.ratioR_c = (float *)(mbase + mr.ratioR); st.ratioL_p = (float *)(mbase + mr.ratioL);
-    st.count = (int *)(mbase + mr.count); st.counts = (int *)(mbase + mr.counts); st.order = (int *)(mbase + mr.order);
-    st.temp = nullptr; st.rstride = (size_t)(n + m); st.gate = flag; st.pm = PairMap{1, 1, 0};
-    u4 *recA2_dense = (u4 *)(mbase + mr.recA2d);
+    const MfmaState st = mfma_state(L, workspace, 1, n, m, nullptr, flag, PairMap{1, 1, 0});
+    u4 *recA2_dense = ws_at<u4>(workspace, L.recA2d);
     hipLaunchKernelGGL(emd_mfma_prep_kernel, dim3(1), dim3(1024), 0, s, n, m, xyz1, xyz2, meta, flag, st.pm);
-    hipLaunchKernelGGL(emd_mfma_pack_kernel, dim3((NP + MP + 255) / 256, 1), dim3(256), 0, s, st, 1.0f, xyz1, xyz2, (const float *)meta,
-                       recA2_dense, (float *)workspace, (size_t)(n + m));
-    const int ex = 2 * (level_j - 7), eF = ex < -14 ? -14 : ex;
-    const LevelFac lf{(unsigned)((eF + 15) << 10), (unsigned)((ex - eF + 15) << 10), (unsigned)((level_j - 7 + 15) << 10)};
-    hipLaunchKernelGGL(emd_mfma_debug_exponents_kernel, dim3(NP / 32, MP / 32), dim3(64), 0, s, st, lf, (const u4 *)recA2_dense, out, slot_mask);
+    hipLaunchKernelGGL(emd_mfma_pack_kernel, dim3((L.NP + L.MP + 255) / 256, 1), dim3(256), 0, s, st, 1.0f, xyz1, xyz2, (const float *)meta,
+                       recA2_dense, (float *)workspace, L.lstride);
+    hipLaunchKernelGGL(emd_mfma_debug_exponents_kernel, dim3(L.NP / 32, L.MP / 32), dim3(64), 0, s, st, level_fac(level_j),
+                       (const u4 *)recA2_dense, out, slot_mask);
     if (meta8) {
         e = hipMemcpyAsync(meta8, meta, METAF * sizeof(float), hipMemcpyDeviceToDevice, s);
         if (e != hipSuccess) return (int)e;
@@ -2060,31 +1977,21 @@ extern "C" int dpf_debug_emd_exponents(int n, int m, const float *xyz1, const fl
     return (int)hipGetLastError();
 }
 
-#if EMD_DBG & 8
-extern "C" int dpf_debug_emd_mismatches(float *out129) {     // EMD_DBG & 8 builds: [count, 16 x 8 records]; resets the count
-    unsigned n = 0;
-    float rec[128];
-    if (hipMemcpyFromSymbol(&n, HIP_SYMBOL(g_emd_dbg_n), 4) != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(rec, HIP_SYMBOL(g_emd_dbg), sizeof(rec)) != hipSuccess) return -1;
-    out129[0] = (float)n;
-    memcpy(out129 + 1, rec, sizeof(rec));
-    n = 0;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_emd_dbg_n), &n, 4);
-    return 0;
-}
-#endif
-
 extern "C" int dpf_approxmatch_ws(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *temp,
                                   void *workspace, size_t workspace_bytes, dpf_stream_t stream) {
     return approxmatch_impl(b, n, m, xyz1, xyz2, match, temp, nullptr, workspace, workspace_bytes, stream);
+}
+
+// The entries that cannot do without the workspace refuse a call without a cost, a workspace or its size before anything else
+static bool cost_ws_missing(int b, int n, int m, const float *cost, const void *workspace, size_t workspace_bytes) {
+    return !cost || !workspace || workspace_bytes < dpf_approxmatch_workspace_bytes(b, n, m);       // (0 for an empty or invalid shape)
 }
 
 // approxmatch + matchcost in one call: the materialisation pass also sums match * distance (fixed-order partial
 // sums: deterministic).  The workspace is required (there is no read-modify-write variant of this entry point).
 extern "C" int dpf_approxmatch_cost_ws(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *temp,
                                        float *cost, void *workspace, size_t workspace_bytes, dpf_stream_t stream) {
-    if (!cost || !workspace || (b > 0 && n > 0 && m > 0 && workspace_bytes < dpf_approxmatch_workspace_bytes(b, n, m)))
-        return DPF_EINVAL;
+    if (cost_ws_missing(b, n, m, cost, workspace, workspace_bytes)) return DPF_EINVAL;
     return approxmatch_impl(b, n, m, xyz1, xyz2, match, temp, cost, workspace, workspace_bytes, stream);
 }
 
@@ -2093,8 +2000,7 @@ extern "C" int dpf_approxmatch_cost_ws(int b, int n, int m, const float *xyz1, c
 // is the saved state of dpf_matchcostgrad_recompute_ws (include/dpf_hip.h lists the regions).
 extern "C" int dpf_approxmatch_costonly_ws(int b, int n, int m, const float *xyz1, const float *xyz2, float *temp, float *cost,
                                            void *workspace, size_t workspace_bytes, dpf_stream_t stream) {
-    if (!cost || !workspace || (b > 0 && n > 0 && m > 0 && workspace_bytes < dpf_approxmatch_workspace_bytes(b, n, m)))
-        return DPF_EINVAL;
+    if (cost_ws_missing(b, n, m, cost, workspace, workspace_bytes)) return DPF_EINVAL;
     return approxmatch_impl(b, n, m, xyz1, xyz2, nullptr, temp, cost, workspace, workspace_bytes, stream, nullptr, true);
 }
 
@@ -2103,30 +2009,33 @@ extern "C" int dpf_approxmatch_costonly_ws(int b, int n, int m, const float *xyz
 // the batched entries pick for PAIRWISE_SLICE_B clouds -- a function of (n, m) alone, so an entry's bits do not depend on how the
 // matrix is cut into launches.  (64 clouds: 4 slices at 2 048 points, 1 from 8 192 -- the launches of a matrix hold hundreds of
 // pairs, and 4 waves per 128 points keep a 64-pair launch at the 4 096 waves the batched choice aims for.)
-// Workspace: [the deferred path's (rows n2 pairs) | temp: rows n2 x 2 (n + m) floats | the verdicts: rows n2 words].
+// Workspace: [the deferred path's (rows n2 pairs) | temp: rows n2 x 2 (n + m) floats | the verdicts: rows n2 words], the first
+// two padded to 64 bytes.
 constexpr int PAIRWISE_SLICE_B = 64;
-static size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
+struct PairwiseLayout { size_t emd_bytes, temp, gates, total; };
+static PairwiseLayout pairwise_layout(int pairs, int n, int m) {
+    auto align64 = [](size_t v) { return (v + 63) & ~(size_t)63; };
+    PairwiseLayout P;
+    P.emd_bytes = P.temp = align64(emd_layout(pairs, n, m).total);
+    P.gates = P.temp + align64((size_t)pairs * 2 * ((size_t)n + m) * sizeof(float));
+    P.total = P.gates + (size_t)pairs * sizeof(unsigned);
+    return P;
+}
 
 extern "C" size_t dpf_pairwise_emd_workspace_bytes(int rows, int n2, int n, int m) {
     if (rows <= 0 || n2 <= 0 || n <= 0 || m <= 0 || (long)rows * n2 > 65535) return 0;
-    const int P = rows * n2;
-    return align64(dpf_approxmatch_workspace_bytes(P, n, m)) + align64((size_t)P * 2 * ((size_t)n + m) * sizeof(float)) +
-           (size_t)P * sizeof(unsigned);
+    return pairwise_layout(rows * n2, n, m).total;
 }
 
 extern "C" int dpf_pairwise_emd(int rows, int n2, int n, int m, const float *clouds1, const float *clouds2, float *cost,
                                 void *workspace, size_t workspace_bytes, dpf_stream_t stream) {
-    if (rows < 0 || n2 < 0 || n <= 0 || m <= 0) return DPF_EINVAL;
-    if (rows == 0 || n2 == 0) return 0;
-    if (!clouds1 || !clouds2 || !cost || !workspace) return DPF_EINVAL;
-    if ((long)rows * n2 > 65535) return DPF_ENOSUP;                       // the pairs are grid y of the per-pair kernels
-    if (workspace_bytes < dpf_pairwise_emd_workspace_bytes(rows, n2, n, m)) return DPF_EINVAL;
-    const int P = rows * n2;
-    const size_t wb = align64(dpf_approxmatch_workspace_bytes(P, n, m));
-    float *temp = (float *)((uint8_t *)workspace + wb);
-    unsigned *gates = (unsigned *)((uint8_t *)temp + align64((size_t)P * 2 * ((size_t)n + m) * sizeof(float)));
-    const PairCall pc{PairMap{n2, n2, 1}, gates, PAIRWISE_SLICE_B};
-    return approxmatch_impl(P, n, m, clouds1, clouds2, nullptr, temp, cost, workspace, wb, stream, &pc);
+    int rc;                                                                // (the pairs are grid y of the per-pair kernels)
+    if (args_settle(rc, rows < 0 || n2 < 0 ? -1 : (long)rows * n2, n, m, clouds1 && clouds2 && cost && workspace)) return rc;
+    const int pairs = rows * n2;
+    const PairwiseLayout P = pairwise_layout(pairs, n, m);
+    if (workspace_bytes < P.total) return DPF_EINVAL;
+    const PairCall pc{PairMap{n2, n2, 1}, ws_at<unsigned>(workspace, P.gates), PAIRWISE_SLICE_B};
+    return approxmatch_impl(pairs, n, m, clouds1, clouds2, nullptr, ws_at<float>(workspace, P.temp), cost, workspace, P.emd_bytes, stream, &pc);
 }
 
 extern "C" int dpf_approxmatch(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *temp,
@@ -2136,10 +2045,8 @@ extern "C" int dpf_approxmatch(int b, int n, int m, const float *xyz1, const flo
 
 extern "C" int dpf_matchcost(int b, int n, int m, const float *xyz1, const float *xyz2, const float *match, float *out,
                              dpf_stream_t stream) {
-    if (b < 0 || n <= 0 || m <= 0) return DPF_EINVAL;
-    if (b == 0) return 0;
-    if (!xyz1 || !xyz2 || !match || !out) return DPF_EINVAL;
-    if (b > 65535) return DPF_ENOSUP;
+    int rc;
+    if (args_settle(rc, b, n, m, xyz1 && xyz2 && match && out)) return rc;
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = dpf_zero_async(out, sizeof(float) * b, s);
     if (e != hipSuccess) return (int)e;
@@ -2152,10 +2059,8 @@ extern "C" int dpf_matchcost(int b, int n, int m, const float *xyz1, const float
 
 extern "C" int dpf_matchcostgrad(int b, int n, int m, const float *xyz1, const float *xyz2, const float *match,
                                  float *grad1, float *grad2, dpf_stream_t stream) {
-    if (b < 0 || n <= 0 || m <= 0) return DPF_EINVAL;
-    if (b == 0) return 0;
-    if (!xyz1 || !xyz2 || !match || !grad1 || !grad2) return DPF_EINVAL;
-    if (b > 65535) return DPF_ENOSUP;
+    int rc;
+    if (args_settle(rc, b, n, m, xyz1 && xyz2 && match && grad1 && grad2)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int s1 = pick_slices(b, n, m);
     hipLaunchKernelGGL(emd_grad1_kernel, dim3((n + 63) / 64, b), dim3(64, s1), 0, s, n, m, xyz1, xyz2, match, grad1);
@@ -2173,10 +2078,8 @@ extern "C" size_t dpf_matchcostgrad_workspace_bytes(int b, int n, int m) {
 extern "C" int dpf_matchcostgrad_ws(int b, int n, int m, const float *xyz1, const float *xyz2, const float *match,
                                     float *grad1, float *grad2, void *workspace, size_t workspace_bytes,
                                     dpf_stream_t stream) {
-    if (b < 0 || n <= 0 || m <= 0) return DPF_EINVAL;
-    if (b == 0) return 0;
-    if (!xyz1 || !xyz2 || !match || !grad1 || !grad2) return DPF_EINVAL;
-    if (b > 65535) return DPF_ENOSUP;
+    int rc;
+    if (args_settle(rc, b, n, m, xyz1 && xyz2 && match && grad1 && grad2)) return rc;
     const int nkb = (n + 255) / 256;
     // one workgroup per 256 columns and cloud: with fewer than one per CU the row-parallel two-pass kernels win
     // (measured r01, one pass vs two kernels: B=2, N=8192: 0.58 vs 0.29 ms; B=32, N=2048: 0.37 vs 0.30 ms;
@@ -2198,50 +2101,36 @@ extern "C" int dpf_matchcostgrad_ws(int b, int n, int m, const float *xyz1, cons
 // 3 / 16 n of the matching's size.  Reads the saved workspace only; allocates nothing, no synchronisation.
 extern "C" size_t dpf_matchcostgrad_recompute_workspace_bytes(int b, int n, int m) {
     if (b <= 0 || n <= 0 || m <= 0) return 0;
-    const size_t NP = (size_t)(n + MPW - 1) / MPW * MPW, MP = (size_t)(m + MPW - 1) / MPW * MPW;
-    return (size_t)b * (NP / (32 * MTM)) * MP * 3 * sizeof(float);         // (>= the packed-VALU family's b ceil(n / 128) m 12)
+    const EmdLayout L = emd_layout(b, n, m);
+    return (size_t)b * (L.NP / (32 * MTM)) * L.MP * 3 * sizeof(float);         // (>= the packed-VALU family's b ceil(n / 128) m 12)
 }
 
 extern "C" int dpf_matchcostgrad_recompute_ws(int b, int n, int m, const float *xyz1, const float *xyz2, const void *saved_workspace,
                                               size_t saved_bytes, float *grad1, float *grad2, void *scratch, size_t scratch_bytes,
                                               dpf_stream_t stream) {
-    if (b < 0 || n <= 0 || m <= 0) return DPF_EINVAL;
-    if (b == 0) return 0;
-    if (!xyz1 || !xyz2 || !saved_workspace || !grad1 || !grad2 || !scratch) return DPF_EINVAL;
-    if (b > 65535) return DPF_ENOSUP;
-    if (saved_bytes < dpf_approxmatch_workspace_bytes(b, n, m) || scratch_bytes < dpf_matchcostgrad_recompute_workspace_bytes(b, n, m))
-        return DPF_EINVAL;
+    int rc;
+    if (args_settle(rc, b, n, m, xyz1 && xyz2 && saved_workspace && grad1 && grad2 && scratch)) return rc;
+    const EmdLayout L = emd_layout(b, n, m, (uintptr_t)saved_workspace);           // the forward's
+    if (saved_bytes < L.total || scratch_bytes < dpf_matchcostgrad_recompute_workspace_bytes(b, n, m)) return DPF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    // the forward's layout (approxmatch_impl)
-    const int NP = (n + MPW - 1) / MPW * MPW, MP = (m + MPW - 1) / MPW * MPW;
     const float *ws = (const float *)saved_workspace;
-    const size_t rstride = (size_t)(n + m), lstride = (size_t)b * (n + m), pstride = (size_t)n + 2 * (size_t)m;
-    const float4 *pk = (const float4 *)(((uintptr_t)(ws + NLEVEL * lstride) + 15) & ~(uintptr_t)15);
-    const float *rec = (const float *)(pk + (size_t)b * pstride);
-    uint8_t *mbase = (uint8_t *)(((uintptr_t)saved_workspace + deferred_bytes(b, n, m) + 63) & ~(uintptr_t)63);
-    const MfmaRegions mr = mfma_regions(b, n, m);
-    const unsigned *words = (const unsigned *)(mbase + mr.flag);
+    const unsigned *words = ws_at<const unsigned>(saved_workspace, L.flag);
     float *part2 = (float *)scratch;
     {   // matrix-core family
-        MfmaState st{};
-        st.n = n; st.m = m; st.NP = NP; st.MP = MP; st.nb = b;
-        st.recB1 = (const u4 *)(mbase + mr.recB1);
-        st.counts = (int *)(mbase + mr.counts);
-        st.rstride = rstride; st.pm = PairMap{1, b, 0};
-        LevelScales ls;
-        for (int lj = 0; lj < NLEVEL; ++lj) ls.lf[lj] = level_fac(7 - lj);
-        const int m1 = pick_mfma_slices(b, n, m), nkb = NP / (32 * MTM);
-        hipLaunchKernelGGL(emd_mfma_grad_kernel, dim3(nkb, b), dim3(64, m1), 0, s, st, ls, words, xyz1, ws, lstride,
-                           (const u4 *)(mbase + mr.recAs), (const float *)(mbase + mr.rrs), (const float *)(mbase + mr.c2s), grad1, part2);
-        hipLaunchKernelGGL(emd_grad2_recompute_sum_kernel<0>, dim3((MP * 3 + 255) / 256, b), dim3(256), 0, s, m, MP, nkb, words,
-                           (const int *)(mbase + mr.ls), (const float *)part2, grad2);
+        const MfmaState st = mfma_state(L, saved_workspace, b, n, m, nullptr, nullptr, PairMap{1, b, 0});
+        const int m1 = pick_mfma_slices(b, n, m), nkb = L.NP / (32 * MTM);
+        hipLaunchKernelGGL(emd_mfma_grad_kernel, dim3(nkb, b), dim3(64, m1), 0, s, st, level_scales(), words, xyz1, ws, L.lstride,
+                           ws_at<const u4>(saved_workspace, L.recAs), ws_at<const float>(saved_workspace, L.rrs),
+                           ws_at<const float>(saved_workspace, L.c2s), grad1, part2);
+        hipLaunchKernelGGL(emd_grad2_recompute_sum_kernel<0>, dim3((L.MP * 3 + 255) / 256, b), dim3(256), 0, s, m, L.MP, nkb, words,
+                           ws_at<const int>(saved_workspace, L.ls), (const float *)part2, grad2);
     }
     {   // packed-VALU family
         const int nkb = (n + PPW - 1) / PPW;
         int gs = 1;
         while (gs < GSL && (long)b * nkb * gs < 2048 && m / (2 * gs) >= 2 * GROWS) gs *= 2;
-        hipLaunchKernelGGL(emd_materialize2_grad_kernel, dim3(nkb, b), dim3(64, gs), 0, s, n, m, level_pairs(), words, xyz1, rec, ws,
-                           lstride, rstride, grad1, part2);
+        hipLaunchKernelGGL(emd_materialize2_grad_kernel, dim3(nkb, b), dim3(64, gs), 0, s, n, m, level_pairs(), words, xyz1,
+                           ws_at<const float>(saved_workspace, L.rec), ws, L.lstride, L.rstride, grad1, part2);
         hipLaunchKernelGGL(emd_grad2_recompute_sum_kernel<1>, dim3((m * 3 + 255) / 256, b), dim3(256), 0, s, m, m, nkb, words,
                            (const int *)nullptr, (const float *)part2, grad2);
     }

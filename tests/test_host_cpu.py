@@ -31,6 +31,33 @@ def test_library_exports_every_declared_symbol():
     assert handle.dpf_flow_film_floats(14, 32) == 14 * 32 * 512
 
 
+def test_approx_emd_workspace_sizes_are_pinned():
+    """The approx-EMD workspace's layout is public (include/dpf_hip.h: the saved state of dpf_matchcostgrad_recompute_ws) and is
+    written down once in csrc/emd.hip (emd_layout).  The totals below were taken from the library of commit 5c94248, whose
+    entries each derived them on their own; the size queries are host-only.  Ragged shapes: n < m, n > m, sizes off the 128-point
+    padding, single points, the largest batch."""
+    from dpf_nets_amd import _lib
+    h = _lib.lib()
+    approx = {(16, 8192, 8192): 74515728, (3, 100, 257): 514268, (1, 1, 1): 51768, (2, 127, 129): 231056, (5, 1000, 300): 1422752,
+              (7, 300, 1000): 3485824, (1, 2048, 1): 289732, (4, 129, 128): 326880, (65535, 3, 5): 3412538736}
+    recompute = {(16, 8192, 8192): 201326592, (3, 100, 257): 27648, (1, 1, 1): 3072, (2, 127, 129): 12288, (5, 1000, 300): 368640,
+                 (7, 300, 1000): 516096, (1, 2048, 1): 49152, (4, 129, 128): 24576, (65535, 3, 5): 201323520}
+    pairwise = {(8, 8, 2048, 2048): 76616640, (3, 5, 100, 257): 2613308, (1, 1, 1, 1): 51844, (2, 9, 300, 1000): 9150536,
+                (255, 257, 3, 5): 3416995132, (256, 256, 3, 5): 0}                    # (more than 65535 pairs: not supported)
+    for shape, want in approx.items():
+        assert h.dpf_approxmatch_workspace_bytes(*shape) == want, shape
+    for shape, want in recompute.items():
+        assert h.dpf_matchcostgrad_recompute_workspace_bytes(*shape) == want, shape
+    align64 = lambda v: (v + 63) // 64 * 64                                          # noqa: E731
+    for (r, c, n, m), want in pairwise.items():
+        assert h.dpf_pairwise_emd_workspace_bytes(r, c, n, m) == want, (r, c, n, m)
+        if want:
+            assert want == align64(h.dpf_approxmatch_workspace_bytes(r * c, n, m)) + align64(r * c * 2 * (n + m) * 4) + r * c * 4
+    for shape in ((0, 4, 4), (-1, 4, 4), (2, 0, 4), (2, 4, -3)):                      # empty or invalid: nothing to allocate
+        assert h.dpf_approxmatch_workspace_bytes(*shape) == 0 and h.dpf_matchcostgrad_recompute_workspace_bytes(*shape) == 0
+    assert h.dpf_pairwise_emd_workspace_bytes(0, 3, 4, 4) == 0 and h.dpf_pairwise_emd_workspace_bytes(3, 3, 4, 0) == 0
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     from dpf_nets_amd import _lib
     monkeypatch.setattr(_lib, "_LIB", None)

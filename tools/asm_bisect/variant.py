@@ -7,8 +7,9 @@ single instructions can be exchanged while everything else (register allocation,
 
     python tools/asm_bisect/variant.py <name> [<name> ...]      (names: see VARIANTS; `all` builds every one)
 
-On the GPU box: tools/asm_bisect/run.sh  (copies each variant over dpf_nets_amd/libdpf_hip.so in the box's scratch copy and runs
-tests/diag/emd_bisect.py on the reproducer).  Scratch tooling: nothing here is part of the product path."""
+r06 ran every variant through tools/asm_bisect/run.sh and tests/diag/emd_bisect.py (the call stopped behind its k-th launch by
+DPF_EMD_STOP_AFTER, a switch csrc/emd.hip had up to commit 5c94248; both scripts went with it -- their results are
+profiles/r06_emd_asm_bisect.txt).  Scratch tooling: nothing here is part of the product path."""
 import os
 import re
 import subprocess
@@ -272,7 +273,7 @@ VARIANTS = {
     "unpack_even": (True, ROWS4, v_unpack_subset(lambda k: k % 2 == 0)),
     "unpack_first_half": (True, ROWS4, v_unpack_subset(lambda k: k < 16)),
     "unpack_second_half": (True, ROWS4, v_unpack_subset(lambda k: k >= 16)),
-    # the columns kernel of pass 1 (the launch whose OUTPUT differs first inside one process: emd_flicker_values.py 5,6)
+    # the columns kernel of pass 1 (the launch whose OUTPUT differs first inside one process: launches 5 and 6)
     "c0_unpack": (True, COLS0, v_unpack_any),
     "c0_nop_war": (True, COLS0, v_nop_behind_mfma_source_overwrite(7)),
     "c0_nop_war8": (True, COLS0, v_nop_behind_mfma_source_overwrite(7, 8)),
