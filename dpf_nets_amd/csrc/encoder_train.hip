@@ -844,32 +844,35 @@ struct TWork {
     uint8_t *aP[3], *wf[3], *wb[3];
     float *part, *cnt, *bnp, *coef, *yarg, *gz, *wpart, *w0part, *tmax, *tmin;
     int *arg;
+    size_t bytes;                // of all regions, each rounded up to 256
 };
-size_t t_carve(void *ws, const Geo &g, TWork *w) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { void *p = ws ? (uint8_t *)ws + off : nullptr; off += (bytes + 255) & ~(size_t)255; return p; };
+TWork t_carve(void *ws, const Geo &g) {                      // ws == nullptr: only .bytes means anything
+    TWork w = {};
+    auto take = [&](auto *&region, size_t bytes) {
+        if (ws) region = (std::remove_reference_t<decltype(region)>)((uint8_t *)ws + w.bytes);
+        w.bytes += (bytes + 255) & ~(size_t)255;
+    };
     const int C[4] = {EC1, EC2, EC3, EC4};
-    void *p;
-    for (int l = 0; l < 4; ++l) { p = take((size_t)C[l] * g.P * 4); if (w) w->y[l] = (float *)p; }
-    for (int l = 0; l < 3; ++l) { p = take((size_t)C[l] * g.P * 4); if (w) w->dz[l] = (float *)p; }
-    for (int l = 0; l < 3; ++l) { p = take((size_t)C[l] * g.P * 4); if (w) w->aP[l] = (uint8_t *)p; }
+    for (int l = 0; l < 4; ++l) take(w.y[l], (size_t)C[l] * g.P * 4);
+    for (int l = 0; l < 3; ++l) take(w.dz[l], (size_t)C[l] * g.P * 4);
+    for (int l = 0; l < 3; ++l) take(w.aP[l], (size_t)C[l] * g.P * 4);
     for (int l = 1; l < 4; ++l) {
-        p = take((size_t)C[l] * C[l - 1] * 6); if (w) w->wf[l - 1] = (uint8_t *)p;
-        p = take((size_t)C[l] * C[l - 1] * 4); if (w) w->wb[l - 1] = (uint8_t *)p;
+        take(w.wf[l - 1], (size_t)C[l] * C[l - 1] * 6);
+        take(w.wb[l - 1], (size_t)C[l] * C[l - 1] * 4);
     }
-    p = take((size_t)g.nwg * 2 * EC4 * 4); if (w) w->part = (float *)p;
-    p = take((size_t)g.nwg * 4); if (w) w->cnt = (float *)p;
-    p = take((size_t)4 * TCSUM * 4); if (w) w->bnp = (float *)p;
-    p = take((size_t)3 * TCSUM * 4); if (w) w->coef = (float *)p;
-    p = take((size_t)g.B * EC4 * 4); if (w) w->yarg = (float *)p;
-    p = take((size_t)g.B * EC4 * 4); if (w) w->gz = (float *)p;
-    p = take((size_t)g.B * EC4 * 4); if (w) w->arg = (int *)p;
+    take(w.part, (size_t)g.nwg * 2 * EC4 * 4);
+    take(w.cnt, (size_t)g.nwg * 4);
+    take(w.bnp, (size_t)4 * TCSUM * 4);
+    take(w.coef, (size_t)3 * TCSUM * 4);
+    take(w.yarg, (size_t)g.B * EC4 * 4);
+    take(w.gz, (size_t)g.B * EC4 * 4);
+    take(w.arg, (size_t)g.B * EC4 * 4);
     const long nchunk = (g.P / 16 + ks_chunk_of(g.P / 16) - 1) / ks_chunk_of(g.P / 16);
-    p = take((size_t)nchunk * EC4 * EC3 * 4); if (w) w->wpart = (float *)p;
-    p = take((size_t)g.B * EC1 * 3 * 4); if (w) w->w0part = (float *)p;
-    p = take((size_t)g.ptiles * EC4 * 4); if (w) w->tmax = (float *)p;
-    p = take((size_t)g.ptiles * EC4 * 4); if (w) w->tmin = (float *)p;
-    return off;
+    take(w.wpart, (size_t)nchunk * EC4 * EC3 * 4);
+    take(w.w0part, (size_t)g.B * EC1 * 3 * 4);
+    take(w.tmax, (size_t)g.ptiles * EC4 * 4);
+    take(w.tmin, (size_t)g.ptiles * EC4 * 4);
+    return w;
 }
 
 inline const float *cW(const float *canon, int l) { return canon + e_layer_off(l); }
@@ -910,45 +913,7 @@ int launch_wgrad(const WArgs &a, int nchunk, int rblocks, int cblocks, hipStream
 
 extern "C" size_t dpf_encoder_train_workspace_bytes(int B, int N) {
     if (B <= 0 || N <= 0) return 0;
-    return t_carve(nullptr, make_geo(B, N), nullptr);
-}
-
-static int encoder_train_forward_direct(int B, int N, int precision, const float *canon, const float *x, void *ws, float *pooled,
-                                        float *batch_stats, float *const *running, float momentum, dpf_stream_t stream);
-static int encoder_train_backward_direct(int B, int N, const float *canon, const float *x, void *ws, const float *pooled,
-                                         const float *g_pooled, float *dcanon, float *dx, dpf_stream_t stream);
-
-// The ~13 (forward) / ~17 (backward) launches of a call as one graph launch once the same call has been seen twice
-// (graph_cache.h): in a training loop the allocator hands back the same workspace, so the steady state is all replays.
-extern "C" int dpf_encoder_train_forward(int B, int N, int precision, const float *canon, const float *x, void *ws, float *pooled,
-                                         float *batch_stats, float *const *running, float momentum, dpf_stream_t stream) {
-    auto direct = [&](hipStream_t st) {
-        return encoder_train_forward_direct(B, N, precision, canon, x, ws, pooled, batch_stats, running, momentum, (dpf_stream_t)st);
-    };
-    static GraphCache cache;
-    GraphKey k;
-    k.val(B); k.val(N); k.val(precision); k.val(canon); k.val(x); k.val(ws); k.val(pooled); k.val(batch_stats); k.val(momentum);
-    const int has_running = running != nullptr;
-    k.val(has_running);
-    if (has_running) k.add(running, sizeof(float *) * 8);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    k.val(dev);
-    return cache.run(k, (hipStream_t)stream, direct);
-}
-
-extern "C" int dpf_encoder_train_backward(int B, int N, const float *canon, const float *x, void *ws, const float *pooled,
-                                          const float *g_pooled, float *dcanon, float *dx, dpf_stream_t stream) {
-    auto direct = [&](hipStream_t st) {
-        return encoder_train_backward_direct(B, N, canon, x, ws, pooled, g_pooled, dcanon, dx, (dpf_stream_t)st);
-    };
-    static GraphCache cache;
-    GraphKey k;
-    k.val(B); k.val(N); k.val(canon); k.val(x); k.val(ws); k.val(pooled); k.val(g_pooled); k.val(dcanon); k.val(dx);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    k.val(dev);
-    return cache.run(k, (hipStream_t)stream, direct);
+    return t_carve(nullptr, make_geo(B, N)).bytes;
 }
 
 static int encoder_train_forward_direct(int B, int N, int precision, const float *canon, const float *x, void *ws, float *pooled,
@@ -960,8 +925,7 @@ static int encoder_train_forward_direct(int B, int N, int precision, const float
     const bool x6 = precision == DPF_PREC_BF16X6;
     hipStream_t s = (hipStream_t)stream;
     const Geo g = make_geo(B, N);
-    TWork w;
-    t_carve(ws, g, &w);
+    const TWork w = t_carve(ws, g);
     const double count = (double)B * N;
     const int C[4] = {EC1, EC2, EC3, EC4};
     // weights -> fragments: forward Bm[k = cin][n = cout] = W[n][k]; backward Bm[k = cout][n = cin] = W[k][n]
@@ -997,8 +961,7 @@ static int encoder_train_backward_direct(int B, int N, const float *canon, const
     if (!canon || !x || !ws || !pooled || !g_pooled || !dcanon) return DPF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const Geo g = make_geo(B, N);
-    TWork w;
-    t_carve(ws, g, &w);
+    const TWork w = t_carve(ws, g);
     const double count = (double)B * N;
     const int C[4] = {EC1, EC2, EC3, EC4};
     const long PS = g.P / 16;
@@ -1035,4 +998,29 @@ static int encoder_train_backward_direct(int B, int N, const float *canon, const
     if (dx != nullptr)
         hipLaunchKernelGGL(et_dx_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, g, w.y[0], w.dz[0], coef0, cW(canon, 0), dx);
     return (int)hipGetLastError();
+}
+
+// The ~13 (forward) / ~17 (backward) launches of a call as one graph launch once the same call has been seen twice
+// (graph_cache.h): in a training loop the allocator hands back the same workspace, so the steady state is all replays.
+extern "C" int dpf_encoder_train_forward(int B, int N, int precision, const float *canon, const float *x, void *ws, float *pooled,
+                                         float *batch_stats, float *const *running, float momentum, dpf_stream_t stream) {
+    auto direct = [&](hipStream_t st) {
+        return encoder_train_forward_direct(B, N, precision, canon, x, ws, pooled, batch_stats, running, momentum, (dpf_stream_t)st);
+    };
+    static GraphCache cache;
+    return dpf_graph_call(cache, (hipStream_t)stream, direct, [&](GraphKey &k) {
+        const int has_running = running != nullptr;
+        k.vals(B, N, precision, canon, x, ws, pooled, batch_stats, momentum, has_running);
+        if (has_running) k.add(running, sizeof(float *) * 8);
+    });
+}
+
+extern "C" int dpf_encoder_train_backward(int B, int N, const float *canon, const float *x, void *ws, const float *pooled,
+                                          const float *g_pooled, float *dcanon, float *dx, dpf_stream_t stream) {
+    auto direct = [&](hipStream_t st) {
+        return encoder_train_backward_direct(B, N, canon, x, ws, pooled, g_pooled, dcanon, dx, (dpf_stream_t)st);
+    };
+    static GraphCache cache;
+    return dpf_graph_call(cache, (hipStream_t)stream, direct,
+                          [&](GraphKey &k) { k.vals(B, N, canon, x, ws, pooled, g_pooled, dcanon, dx); });
 }

@@ -933,10 +933,6 @@ __global__ __launch_bounds__(FW * 64, 2) void flow_kernel(FlowArgs a) {
 #ifdef DPF_PROFILE
 unsigned long long *g_prof = nullptr;
 #endif
-int ns_of(int precision) {   // number of operand parts; DPF_PREC_F16X3 shares the hi/lo layout of bf16x3
-    return precision == DPF_PREC_BF16 ? 1 : (precision == DPF_PREC_BF16X3 || precision == DPF_PREC_F16X3) ? 2
-           : precision == DPF_PREC_BF16X6 ? 3 : 0;
-}
 
 template <int NS, int FW, int LPB, bool PIPE, bool F16, bool SKEW, bool INV>
 int launch_flow_dir(const FlowArgs &a, hipStream_t s) {

@@ -200,6 +200,10 @@ constexpr int P16_A1 = 2 * P16_A1_PART;
 constexpr int P16_A0 = 8192;
 constexpr int P16_LAYER = P16_A1 + P16_A0;
 
+inline int ns_of(int precision) {   // number of operand parts; DPF_PREC_F16X3 shares the hi/lo layout of bf16x3
+    return precision == DPF_PREC_BF16 ? 1 : (precision == DPF_PREC_BF16X3 || precision == DPF_PREC_F16X3) ? 2
+           : precision == DPF_PREC_BF16X6 ? 3 : 0;
+}
 
 }  // namespace
 

@@ -2081,9 +2081,16 @@ __global__ void tprof_set_kernel(unsigned long long *p) { g_tprof = p; }
 
 }  // namespace
 
-// operand parts of the forward contraction; DPF_PREC_F16X3 shares the hi/lo layout of bf16x3 with fp16 values (r03)
-static inline int t_ns(int precision) {
-    return (precision == DPF_PREC_BF16X3 || precision == DPF_PREC_F16X3) ? 2 : (precision == DPF_PREC_BF16X6 ? 3 : 0);
+// operand parts of the forward contraction (0: a precision the training path does not have)
+static inline int t_ns(int precision) { return ns_of(precision) >= 2 ? ns_of(precision) : 0; }
+
+// The one place that maps a precision to the kernels' <NS, F16>: f(ns, f16) gets them as integral constants
+template <class F>
+static int with_precision(int precision, F &&f) {
+    if (precision == DPF_PREC_F16X3) return f(std::integral_constant<int, 2>{}, std::true_type{});
+    if (precision == DPF_PREC_BF16X3) return f(std::integral_constant<int, 2>{}, std::false_type{});
+    if (precision == DPF_PREC_BF16X6) return f(std::integral_constant<int, 3>{}, std::false_type{});
+    return DPF_ENOSUP;
 }
 
 extern "C" size_t dpf_flow_train_canon_floats(void) { return (size_t)T_LAYER; }
@@ -2093,50 +2100,47 @@ extern "C" size_t dpf_flow_train_packed_bytes(int n_layers, int precision) {
 extern "C" size_t dpf_flow_train_stats_floats(void) { return (size_t)ST_LAYER; }
 extern "C" size_t dpf_flow_train_film_floats(int B) { return (size_t)B * (512 + FB_CLOUD); }
 
-static inline int t_nblk(int B, int N) { return B * ((N + TBLK - 1) / TBLK); }
-
 struct TWork {
     double *xpart, *sums, *tot2;
     float *part1, *pc, *s12, *part2, *dout, *ubuf, *coef;
-    unsigned *tickets;           // the arrival counters of the role workgroups: word B = column sums in pass 1, word B + 1 = means in pass 2 (words [0, B): unused since r05)
+    // words [0, B): pass 1's per-cloud tickets when the role workgroups are off (each returns to zero with its cloud's last
+    // workgroup); the role workgroups' arrival counters, monotonic over a call: word B = column sums in pass 1, word B + 1 =
+    // means in pass 2
+    unsigned *tickets;
+    size_t bytes;                // of all regions, each rounded up to 256
 };
-static size_t carve(void *ws, int B, int N, TWork *w) {
-    const size_t nblk = (size_t)t_nblk(B, N), nbx = (size_t)B * ((N + TILE - 1) / TILE);   // the flow kernel's smallest workgroup is one tile
-    uint8_t *p = (uint8_t *)ws;
-    auto take = [&](size_t bytes) { uint8_t *q = p; p += (bytes + 255) / 256 * 256; return q; };
-    uint8_t *xpart = take(nbx * 8 * sizeof(double));
-    uint8_t *sums = take(256 * sizeof(double));
-    uint8_t *tot2 = take(2 * P2_J * sizeof(double));
-    uint8_t *part1 = take(nblk * 520 * 4);
-    uint8_t *pc = take((size_t)B * 520 * 4);
-    uint8_t *tickets = take((size_t)(B + 16) * 4);                      // + the arrival counter of the fused column sums (word B)
-    uint8_t *s12 = take(256 * 4);
-    uint8_t *part2 = take(nblk * 2 * P2_J * 4);
-    uint8_t *dout = take((size_t)B * 4 * N * 4);
-    uint8_t *ubuf = take((size_t)2 * B * 2 * N * 4);                     // two planes (branch-split pass 2 writes one per branch)
-    uint8_t *coef = take(8 * 4);
-    if (w) {
-        w->xpart = (double *)xpart; w->sums = (double *)sums; w->tot2 = (double *)tot2; w->part1 = (float *)part1;
-        w->tickets = (unsigned *)tickets;
-        w->pc = (float *)pc; w->s12 = (float *)s12; w->part2 = (float *)part2; w->dout = (float *)dout;
-        w->ubuf = (float *)ubuf; w->coef = (float *)coef;
-    }
-    return (size_t)(p - (uint8_t *)ws);
+static TWork carve(void *ws, int B, int N) {                 // ws == nullptr: only .bytes means anything
+    const size_t nblk = (size_t)B * ((N + TBLK - 1) / TBLK), nbx = (size_t)B * ((N + TILE - 1) / TILE);   // the flow kernel's smallest workgroup is one tile
+    TWork w = {};
+    auto take = [&](auto *&region, size_t bytes) {
+        if (ws) region = (std::remove_reference_t<decltype(region)>)((uint8_t *)ws + w.bytes);
+        w.bytes += (bytes + 255) / 256 * 256;
+    };
+    take(w.xpart, nbx * 8 * sizeof(double));
+    take(w.sums, 256 * sizeof(double));
+    take(w.tot2, 2 * P2_J * sizeof(double));
+    take(w.part1, nblk * 520 * 4);
+    take(w.pc, (size_t)B * 520 * 4);
+    take(w.tickets, (size_t)(B + 16) * 4);
+    take(w.s12, 256 * 4);
+    take(w.part2, nblk * 2 * P2_J * 4);
+    take(w.dout, (size_t)B * 4 * N * 4);
+    take(w.ubuf, (size_t)2 * B * 2 * N * 4);                             // two planes (branch-split pass 2 writes one per branch)
+    take(w.coef, 8 * 4);
+    return w;
 }
 // workspace for one layer call, forward or backward (contents do not survive the call)
 extern "C" size_t dpf_flow_train_workspace_bytes(int B, int N) {
     if (B <= 0 || N <= 0) return 0;
-    return carve(nullptr, B, N, nullptr) + 256;
+    return carve(nullptr, B, N).bytes + 256;
 }
 
 extern "C" int dpf_flow_train_pack(int n_layers, int precision, const float *tcanon, void *packed, dpf_stream_t stream) {
-    const int ns = t_ns(precision);
     if (n_layers <= 0 || !tcanon || !packed) return DPF_EINVAL;
-    if (!ns) return DPF_ENOSUP;
-    if (precision == DPF_PREC_F16X3) hipLaunchKernelGGL((tpack_kernel<2, true>), dim3(n_layers), dim3(256), 0, (hipStream_t)stream, tcanon, (uint8_t *)packed);
-    else if (ns == 2) hipLaunchKernelGGL(tpack_kernel<2>, dim3(n_layers), dim3(256), 0, (hipStream_t)stream, tcanon, (uint8_t *)packed);
-    else hipLaunchKernelGGL(tpack_kernel<3>, dim3(n_layers), dim3(256), 0, (hipStream_t)stream, tcanon, (uint8_t *)packed);
-    return (int)hipGetLastError();
+    return with_precision(precision, [&](auto ns, auto f16) {
+        hipLaunchKernelGGL((tpack_kernel<ns, f16>), dim3(n_layers), dim3(256), 0, (hipStream_t)stream, tcanon, (uint8_t *)packed);
+        return (int)hipGetLastError();
+    });
 }
 
 // ---- per-kernel timing of the training stack (diagnostics: bench.py's `roofline.kernels`) ---------------------------
@@ -2195,178 +2199,190 @@ extern "C" int dpf_train_kernel_times(int enable, double *us_out, long *calls_ou
     return 0;
 }
 
-template <int NS, bool F16 = false>
-static int prepare_layer(int B, int N, int ka, int kb, const float *tcanon_l, void *packed_l, const float *fm_l,
-                         const float *p_in, float *stats_l, float *film_l, float flow_eps, void *workspace, hipStream_t s,
-                         int xrows) {
-    TWork w;
-    carve(workspace, B, N, &w);
+// ---- the environment switches and the kernel forms they (or the measured thresholds) choose ---------------------------
+// Read once per process, at the first training call: DPF_TRAIN_SPLIT / DPF_TRAIN_ROLES (-1 = not set: the thresholds below
+// decide; 0 / 1 forces the form), DPF_TRAIN_FUSE_COLSUM (default 1) and the current device's CU count.
+struct TrainSwitches { int split, roles, fuse_colsum, n_cu; };
+struct TrainForm { bool split_h1, split1, split2, roles, fuse_colsum; };   // the forms of a layer's kernels at nblk ordinary workgroups per launch
+static TrainForm train_form(int ns, int nblk) {
+    static const TrainSwitches sw = [] {
+        auto env = [](const char *name, int unset) { return getenv(name) ? atoi(getenv(name)) : unset; };
+        int dev = 0, n = 0;
+        (void)hipGetDevice(&dev);
+        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        return TrainSwitches{env("DPF_TRAIN_SPLIT", -1), env("DPF_TRAIN_ROLES", -1), env("DPF_TRAIN_FUSE_COLSUM", 1), n > 0 ? n : 256};
+    }();
+    const bool forced = sw.split >= 0, on = sw.split != 0;
+    TrainForm f;
+    // small batches: the two conditioner branches in two workgroups each (at most half a workgroup per CU otherwise).  r04,
+    // B = 8: tstats_h1 9.5 -> 8.7 us; at 128 workgroups -- B = 16 -- the statistics and pass 1 are better off unsplit (tbwd1
+    // 15.7 us unsplit, 18.1 split), only pass 2 gains
+    f.split_h1 = f.split1 = forced ? on : nblk <= 64;
+    // (bf16x6's three forward parts do not leave the one-branch-per-wave form its registers: that precision keeps one branch per workgroup)
+    f.split2 = ns == 3 || (forced ? on : nblk <= 128);
+    // Who finishes pass 1 -- per-cloud totals, FiLM gradients, dW2 / db2, the BN1-backward means?  Pass 2 needs a CU per workgroup
+    // (158 KB of LDS): role workgroups at the front of its grid (MeansJob) cost nothing where CUs are idle and a whole round of
+    // late workgroups where they are not.  So: roles while the ordinary workgroups + MJ_ROLES fit the chip's CUs, else pass 1's
+    // per-cloud ticket and a recomputation of the means by every workgroup of pass 2 (r02-r04).  DPF_TRAIN_ROLES=0/1 forces either.
+    // (the role form is built for the one-branch-per-workgroup kernel only: that is the form small batches run)
+    f.roles = f.split2 && (sw.roles >= 0 ? sw.roles != 0 : 2 * nblk + MJ_ROLES <= sw.n_cu);
+    // r04: the column sums of the layer above's pass-2 partials ride in pass 1's launch (ColsumJob) instead of a tcolsum launch
+    // of their own between the two layers; DPF_TRAIN_FUSE_COLSUM=0 keeps the separate launch
+    f.fuse_colsum = sw.fuse_colsum != 0;
+    return f;
+}
+
+// What the layers of one stack call share, forward or backward: the checked sizes, the floats per layer of the (L, ...)
+// blocks (lst: ps / mus / logvars and their gradients, fls: film, fms: fm / dfm), the carved workspace and the stream.
+struct StackCall { int B, N, mode, ns; size_t lst, fls, fms; float eps; TWork w; hipStream_t s; };
+// the checks of a stack call and their order (ptrs: every pointer the call needs is there), then the above
+static int stack_open(int n_layers, int B, int N, int mode, int precision, bool ptrs, float flow_eps, void *workspace, hipStream_t s,
+                      StackCall *c) {
+    if (n_layers <= 0 || B <= 0 || N <= 0 || !ptrs) return DPF_EINVAL;
+    if (mode != DPF_MODE_DIRECT && mode != DPF_MODE_INVERSE) return DPF_EINVAL;
+    if (!t_ns(precision) || B > 65535) return DPF_ENOSUP;
+    *c = StackCall{B, N, mode, t_ns(precision), (size_t)B * 3 * N, dpf_flow_train_film_floats(B), (size_t)4 * B * DPF_FLOW_F, flow_eps,
+                   carve(workspace, B, N), s};
+    return 0;
+}
+
+// the kernel arguments every per-layer kernel shares; m = the layer's {ka, kb, wa, wb} (wa, wb, mode stay 0: only the
+// backward passes read them)
+static TArgs layer_args(const StackCall &c, const int *m, const void *packed_l, const float *tcanon_l, const float *film_l,
+                        const float *stats_l, const float *p_in) {
+    TArgs a = {};
+    a.packed_l = (const uint8_t *)packed_l; a.tcanon_l = tcanon_l; a.film_l = film_l; a.filmb_l = film_l + (size_t)c.B * 512;
+    a.stats_l = stats_l; a.p_in = p_in; a.B = c.B; a.N = c.N; a.ka = m[0]; a.kb = m[1]; a.eps = c.eps; a.negone = -1.0f;
+    return a;
+}
+
+template <int NS, bool F16>
+static int prepare_layer(const StackCall &c, const int *m, const float *tcanon_l, void *packed_l, const float *fm_l, const float *p_in,
+                         float *stats_l, float *film_l, int xrows) {
+    const int B = c.B, N = c.N;
+    const TWork &w = c.w; const hipStream_t s = c.s;
     // moments of the layer's input: left behind by the previous layer's flow kernel (xrows partial rows per cloud), or
     // computed here for the first layer of the call
     const int nbx = xrows > 0 ? xrows : (N + 255) / 256;
     const double count = (double)B * N;
-    if (xrows <= 0) { KScope ks(0, s); hipLaunchKernelGGL(tstats_x_kernel, dim3(nbx, B), dim3(256), 0, s, N, ka, kb, p_in, w.xpart); }
-    TArgs a;
-    a.packed_l = (const uint8_t *)packed_l; a.tcanon_l = tcanon_l; a.film_l = film_l; a.filmb_l = film_l + (size_t)B * 512;
-    a.stats_l = stats_l; a.p_in = p_in; a.B = B; a.N = N; a.ka = ka; a.kb = kb; a.wa = 0; a.wb = 0; a.mode = 0;
-    a.eps = flow_eps; a.negone = -1.0f;
+    if (xrows <= 0) { KScope ks(0, s); hipLaunchKernelGGL(tstats_x_kernel, dim3(nbx, B), dim3(256), 0, s, N, m[0], m[1], p_in, w.xpart); }
+    const TArgs a = layer_args(c, m, packed_l, tcanon_l, film_l, stats_l, p_in);
     static LdsLimit lim_h1;
     if (hipError_t e = lim_h1.ensure((const void *)tstats_h1_kernel<NS, F16>, pt_a0n(NS)); e != hipSuccess) return (int)e;
     const dim3 grid((N + TBLK - 1) / TBLK, B);
-    static const int split_env = getenv("DPF_TRAIN_SPLIT") ? atoi(getenv("DPF_TRAIN_SPLIT")) : -1;
-    // one branch per workgroup for small batches (r04, B = 8: 9.5 -> 8.7 us; at 128 workgroups -- B = 16 -- passes 1 and the
-    // statistics are better off unsplit, only pass 2 gains)
-    const bool split = split_env >= 0 ? split_env != 0 : (int)(grid.x * grid.y) <= 64;
+    const bool split = train_form(NS, (int)(grid.x * grid.y)).split_h1;
     { KScope ks(1, s);
     hipLaunchKernelGGL((tstats_h1_kernel<NS, F16>), dim3(grid.x, grid.y, split ? 2 : 1), dim3(TW * 64), pt_a0n(NS), s, a, w.part1, nbx * B, count, w.xpart,
                        (uint8_t *)packed_l + pt_a0(NS)); }
     { KScope ks(2, s);
-    hipLaunchKernelGGL(tfold_kernel, dim3(8), dim3(1024), 0, s, count, (int)(grid.x * grid.y), w.part1, tcanon_l, fm_l, B, flow_eps,
+    hipLaunchKernelGGL(tfold_kernel, dim3(8), dim3(1024), 0, s, count, (int)(grid.x * grid.y), w.part1, tcanon_l, fm_l, B, c.eps,
                        stats_l, film_l, film_l + (size_t)B * 512, F16 ? (const float *)((const uint8_t *)packed_l + pt_tail(NS)) : nullptr); }
     return (int)hipGetLastError();
 }
 
 // Training-mode forward of an L-layer stack: per layer (in the order the mode prescribes) the batch statistics
-// and folds, then the layer itself through dpf_flow_forward(n_layers = 1).
-static int flow_train_forward_direct(int n_layers, int B, int N, int mode, int precision, const int *meta_host,
-                                     const int *meta_dev, const float *tcanon, void *packed, const float *fm,
-                                     const float *p_in, float *ps, float *mus, float *logvars, float *stats, float *film,
-                                     float flow_eps, void *workspace, dpf_stream_t stream) {
-    if (n_layers <= 0 || B <= 0 || N <= 0 || !meta_host || !meta_dev || !tcanon || !packed || !fm || !p_in || !ps || !mus ||
-        !logvars || !stats || !film || !workspace)
-        return DPF_EINVAL;
-    if (mode != DPF_MODE_DIRECT && mode != DPF_MODE_INVERSE) return DPF_EINVAL;
-    const int ns = t_ns(precision);
-    if (!ns || B > 65535) return DPF_ENOSUP;
-    const size_t lst = (size_t)B * 3 * N, fls = dpf_flow_train_film_floats(B), fms = (size_t)4 * B * DPF_FLOW_F;
-    const float *cur = p_in;
-    TWork w;
-    carve(workspace, B, N, &w);
-    int xrows = 0;                                   // partial rows per cloud the previous layer's kernel left in w.xpart
-    for (int step = 0; step < n_layers; ++step) {
-        const int l = mode == DPF_MODE_DIRECT ? step : n_layers - 1 - step;
-        const int *m = meta_host + 4 * l;
-        uint8_t *pk = (uint8_t *)packed + (size_t)l * pt_bytes(ns);
-        float *film_l = film + l * fls;
-#define DPF_PREP(...)                                                                                                    \
-    prepare_layer<__VA_ARGS__>(B, N, m[0], m[1], tcanon + (size_t)l * T_LAYER, pk, fm + l * fms, cur,                    \
-                               stats + (size_t)l * ST_LAYER, film_l, flow_eps, workspace, (hipStream_t)stream, xrows)
-        int rc = precision == DPF_PREC_F16X3 ? DPF_PREP(2, true) : (ns == 2 ? DPF_PREP(2) : DPF_PREP(3));
-#undef DPF_PREP
-        if (rc) return rc;
-        // the layer itself; its epilogue leaves the moments of the NEXT layer's kept coordinates (w.xpart was consumed by
-        // this layer's tstats_h1 above)
-        xrows = 0;
-        KScope ks_flow(3, (hipStream_t)stream);
-        if (step + 1 < n_layers) {
-            const int *mnext = meta_host + 4 * (mode == DPF_MODE_DIRECT ? l + 1 : l - 1);
-            rc = flow_forward_xstats(B, N, mode, precision, pk, meta_dev + 4 * l, film_l, cur, ps + l * lst, mus + l * lst,
-                                     logvars + l * lst, flow_eps, stream, w.xpart, mnext[0], mnext[1], &xrows);
-        } else {
-            // (the csrc-internal entry, not dpf_flow_forward: `pk` is tpack_kernel's 32-point-tile block -- the public entry
-            // would hand a small batch to the 16-point-tile kernel, whose fragments dpf_flow_pack lays out)
-            rc = flow_forward_xstats(B, N, mode, precision, pk, meta_dev + 4 * l, film_l, cur, ps + l * lst, mus + l * lst,
-                                     logvars + l * lst, flow_eps, stream, nullptr, 0, -1, nullptr);
-        }
-        if (rc) return rc;
-        cur = ps + l * lst;
-    }
-    return 0;
-}
-
+// and folds, then the layer itself through flow_forward_xstats(n_layers = 1).
 // The stack's ~6 n_layers launches as one graph launch once the same call has been seen twice (graph_cache.h)
 extern "C" int dpf_flow_train_forward(int n_layers, int B, int N, int mode, int precision, const int *meta_host,
                                       const int *meta_dev, const float *tcanon, void *packed, const float *fm,
                                       const float *p_in, float *ps, float *mus, float *logvars, float *stats, float *film,
                                       float flow_eps, void *workspace, dpf_stream_t stream) {
-    auto direct = [&](hipStream_t st) {
-        return flow_train_forward_direct(n_layers, B, N, mode, precision, meta_host, meta_dev, tcanon, packed, fm, p_in, ps, mus,
-                                         logvars, stats, film, flow_eps, workspace, (dpf_stream_t)st);
+    auto direct = [&](hipStream_t st) -> int {
+        StackCall c;
+        if (int rc = stack_open(n_layers, B, N, mode, precision, meta_host && meta_dev && tcanon && packed && fm && p_in && ps && mus &&
+                                logvars && stats && film && workspace, flow_eps, workspace, st, &c))
+            return rc;
+        const float *cur = p_in;
+        int xrows = 0;                               // partial rows per cloud the previous layer's kernel left in c.w.xpart
+        for (int step = 0; step < n_layers; ++step) {
+            const int l = mode == DPF_MODE_DIRECT ? step : n_layers - 1 - step;
+            uint8_t *pk = (uint8_t *)packed + (size_t)l * pt_bytes(c.ns);
+            float *film_l = film + l * c.fls, *p_l = ps + l * c.lst;
+            int rc = with_precision(precision, [&](auto ns, auto f16) {
+                return prepare_layer<ns, f16>(c, meta_host + 4 * l, tcanon + (size_t)l * T_LAYER, pk, fm + l * c.fms, cur,
+                                              stats + (size_t)l * ST_LAYER, film_l, xrows);
+            });
+            if (rc) return rc;
+            // the layer itself; unless it is the last, its epilogue leaves the moments of the NEXT layer's kept coordinates
+            // (c.w.xpart was consumed by this layer's tstats_h1 above).  The csrc-internal entry, not dpf_flow_forward: `pk`
+            // is tpack_kernel's 32-point-tile block -- the public entry would hand a small batch to the 16-point-tile kernel,
+            // whose fragments dpf_flow_pack lays out
+            const int *mnext = step + 1 < n_layers ? meta_host + 4 * (mode == DPF_MODE_DIRECT ? l + 1 : l - 1) : nullptr;
+            xrows = 0;
+            KScope ks_flow(3, st);
+            rc = flow_forward_xstats(B, N, mode, precision, pk, meta_dev + 4 * l, film_l, cur, p_l, mus + l * c.lst, logvars + l * c.lst,
+                                     flow_eps, (dpf_stream_t)st, mnext ? c.w.xpart : nullptr, mnext ? mnext[0] : 0, mnext ? mnext[1] : -1,
+                                     mnext ? &xrows : nullptr);
+            if (rc) return rc;
+            cur = p_l;
+        }
+        return 0;
     };
     if (n_layers <= 0 || !meta_host) return direct((hipStream_t)stream);
     static GraphCache cache;
-    GraphKey k;
-    k.val(n_layers); k.val(B); k.val(N); k.val(mode); k.val(precision); k.add(meta_host, sizeof(int) * 4 * n_layers);
-    k.val(meta_dev); k.val(tcanon); k.val(packed); k.val(fm); k.val(p_in); k.val(ps); k.val(mus); k.val(logvars); k.val(stats);
-    k.val(film); k.val(flow_eps); k.val(workspace);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    k.val(dev);
-    return cache.run(k, (hipStream_t)stream, direct);
+    return dpf_graph_call(cache, (hipStream_t)stream, direct, [&](GraphKey &k) {
+        k.vals(n_layers, B, N, mode, precision); k.add(meta_host, sizeof(int) * 4 * n_layers);
+        k.vals(meta_dev, tcanon, packed, fm, p_in, ps, mus, logvars, stats, film, flow_eps, workspace);
+    });
 }
 
-template <int NS, bool F16 = false>
-static int backward_layer(int B, int N, int mode, int ka, int kb, int wa, int wb, const float *tcanon_l, const void *packed_l,
-                          const float *film_l, const float *stats_l, const float *p_in, const float *mu_l, const float *lv_l,
-                          const float *g_p, const float *g_p2, const float *g_mu, const float *g_lv, float *dp_in, float *dcanon_l,
-                          float *dfm_l, float flow_eps, void *workspace, hipStream_t s, PrevLayer *pv, int *pass2_launches, bool last) {
-    TWork w;
-    carve(workspace, B, N, &w);
-    TArgs a;
-    a.packed_l = (const uint8_t *)packed_l; a.tcanon_l = tcanon_l; a.film_l = film_l; a.filmb_l = film_l + (size_t)B * 512;
-    a.stats_l = stats_l; a.p_in = p_in; a.B = B; a.N = N; a.ka = ka; a.kb = kb; a.wa = wa; a.wb = wb; a.mode = mode;
-    a.eps = flow_eps; a.negone = -1.0f;
+// pass 2 in one of its forms: one branch per workgroup, a tile per wave (split2), or PAIR (two-part precisions only): one
+// branch per wave, two tiles per wave
+template <int NS, bool F16, bool PAIR, bool ROLES>
+static int launch_pass2(dim3 grid2, hipStream_t s, const TArgs &a, const MeansJob &mj, double count, float *dcanon_l, const TWork &w) {
+    constexpr int lds2 = l_red(NS) + 4096 + TW * XY_WAVE * 2;
+    static LdsLimit lim;
+    if (hipError_t e = lim.ensure((const void *)tbwd2_kernel<NS, F16, PAIR, ROLES>, lds2); e != hipSuccess) return (int)e;
+    KScope ks(5, s);
+    hipLaunchKernelGGL((tbwd2_kernel<NS, F16, PAIR, ROLES>), grid2, dim3(TW * 64), lds2, s, a, mj, count, dcanon_l, w.dout, w.ubuf, w.part2);
+    return 0;
+}
+
+template <int NS, bool F16>
+static int backward_layer(const StackCall &c, const int *m, const float *tcanon_l, const void *packed_l, const float *film_l,
+                          const float *stats_l, const float *p_in, const float *mu_l, const float *lv_l, const float *g_p,
+                          const float *g_p2, const float *g_mu, const float *g_lv, float *dp_in, float *dcanon_l, float *dfm_l,
+                          PrevLayer *pv, int *pass2_launches, bool last) {
+    const int B = c.B, N = c.N, ka = m[0], kb = m[1];
+    const TWork &w = c.w; const hipStream_t s = c.s;
+    TArgs a = layer_args(c, m, packed_l, tcanon_l, film_l, stats_l, p_in);
+    a.wa = m[2]; a.wb = m[3]; a.mode = c.mode;
     const dim3 grid((N + TBLK - 1) / TBLK, B);
     const int nblk = grid.x * grid.y;
     const double count = (double)B * N;
-    const int lds1 = pt_a0n(NS) + 4096 + (TW * 520 + 256 + TW * 64 + 8 + 24) * 4, lds2 = l_red(NS) + 4096 + TW * XY_WAVE * 2;
+    const int lds1 = pt_a0n(NS) + 4096 + (TW * 520 + 256 + TW * 64 + 8 + 24) * 4;
     static LdsLimit lim_b1;
     if (hipError_t e = lim_b1.ensure((const void *)tbwd1_kernel<NS, F16>, lds1); e != hipSuccess) return (int)e;
     static LdsLimit lim_b1s;
     if (hipError_t e = lim_b1s.ensure((const void *)tbwd1_kernel<NS, F16, true>, lds1); e != hipSuccess) return (int)e;
-    // r04: the column sums of the layer above's pass-2 partials ride in this launch (ColsumJob) instead of a tcolsum launch
-    // of their own between the two layers; DPF_TRAIN_FUSE_COLSUM=0 keeps the separate launch
-    static const int fuse_env = getenv("DPF_TRAIN_FUSE_COLSUM") ? atoi(getenv("DPF_TRAIN_FUSE_COLSUM")) : 1;
+    const TrainForm form = train_form(NS, nblk);
+    const bool fuse = form.fuse_colsum;
     ColsumJob cs = {};
     dim3 grid1 = grid;
-    if (fuse_env && pv->has) {
+    if (fuse && pv->has) {
         cs.part2 = w.part2; cs.tot = w.tot2; cs.dcanon_prev = pv->dcanon_l; cs.flag = w.tickets + B; cs.nrows = nblk;
         cs.target = (unsigned)CS_CRIT * (unsigned)(++pv->fused_launches);
         cs.rows = (CS_CRIT + (int)grid.x - 1) / (int)grid.x;
         grid1.y = cs.rows + B + (2 * P2_J / 32 - CS_CRIT / 2 + grid.x - 1) / grid.x;
     }
-    // small batches: the two branches of passes 1 and 2 in two workgroups each (at most half a workgroup per CU otherwise)
-    static const int split_env = getenv("DPF_TRAIN_SPLIT") ? atoi(getenv("DPF_TRAIN_SPLIT")) : -1;
-    // (bf16x6's three forward parts do not leave the one-branch-per-wave form its registers: that precision keeps one branch per workgroup)
-    const bool split2 = NS == 3 || (split_env >= 0 ? split_env != 0 : nblk <= 128);
-    const bool split1 = split_env >= 0 ? split_env != 0 : nblk <= 64;      // (B = 16: tbwd1 15.7 us unsplit, 18.1 split)
-    grid1.z = split1 ? 2 : 1;
-    // Who finishes pass 1 -- per-cloud totals, FiLM gradients, dW2 / db2, the BN1-backward means?  Pass 2 needs a CU per workgroup
-    // (158 KB of LDS): role workgroups at the front of its grid (MeansJob) cost nothing where CUs are idle and a whole round of
-    // late workgroups where they are not.  So: roles while the ordinary workgroups + MJ_ROLES fit the chip's CUs, else pass 1's
-    // per-cloud ticket and a recomputation of the means by every workgroup of pass 2 (r02-r04).  DPF_TRAIN_ROLES=0/1 forces either.
-    static const int roles_env = getenv("DPF_TRAIN_ROLES") ? atoi(getenv("DPF_TRAIN_ROLES")) : -1;
-    static const int n_cu = [] { int dev = 0, n = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
-    const int wg2 = nblk * (split2 ? 2 : 1);
-    // (the role form is built for the one-branch-per-workgroup kernel only: that is the form small batches run)
-    const bool roles = split2 && (roles_env >= 0 ? roles_env != 0 : wg2 + MJ_ROLES <= n_cu);
+    grid1.z = form.split1 ? 2 : 1;
     { KScope ks(4, s);
-    unsigned *tk = roles ? nullptr : w.tickets;
-    if (split1)
-        hipLaunchKernelGGL((tbwd1_kernel<NS, F16, true>), grid1, dim3(TW * 64), lds1, s, a, g_p, g_p2, g_mu, g_lv, mu_l, lv_l, dp_in, w.dout, w.part1, *pv, tk, w.pc, dfm_l, cs);
-    else
-        hipLaunchKernelGGL((tbwd1_kernel<NS, F16>), grid1, dim3(TW * 64), lds1, s, a, g_p, g_p2, g_mu, g_lv, mu_l, lv_l, dp_in, w.dout, w.part1, *pv, tk, w.pc, dfm_l, cs); }
-    MeansJob mj;
+    hipLaunchKernelGGL((form.split1 ? tbwd1_kernel<NS, F16, true> : tbwd1_kernel<NS, F16>), grid1, dim3(TW * 64), lds1, s, a, g_p, g_p2, g_mu, g_lv,
+                       mu_l, lv_l, dp_in, w.dout, w.part1, *pv, form.roles ? nullptr : w.tickets, w.pc, dfm_l, cs); }
+    MeansJob mj = {};
     mj.part1 = w.part1; mj.pc = w.pc; mj.dfm_l = dfm_l; mj.s12 = w.s12; mj.flag = w.tickets + B + 1; mj.nb = (int)grid.x;
-    mj.target = 0; mj.rows = 0;
-    if (roles) {
+    if (form.roles) {
         mj.target = (unsigned)MJ_ROLES * (unsigned)(++*pass2_launches);
         mj.rows = (MJ_ROLES + (int)grid.x - 1) / (int)grid.x;
     }
-    const dim3 grid2(grid.x, mj.rows + grid.y, split2 ? 2 : 1);
-    // split2: one branch per workgroup, a tile per wave; else (two-part precisions): one branch per wave, two tiles per wave
-#define DPF_P2(PAIRV, ROLESV, LDSV)                                                                                                  \
-    {                                                                                                                               \
-        static LdsLimit lim;                                                                                                        \
-        if (hipError_t e = lim.ensure((const void *)tbwd2_kernel<NS, F16, PAIRV, ROLESV>, LDSV); e != hipSuccess) return (int)e;    \
-        KScope ks(5, s);                                                                                                            \
-        hipLaunchKernelGGL((tbwd2_kernel<NS, F16, PAIRV, ROLESV>), grid2, dim3(TW * 64), LDSV, s, a, mj, count, dcanon_l, w.dout, w.ubuf, w.part2); \
-    }
-    if (split2) { if (roles) DPF_P2(false, true, lds2) else DPF_P2(false, false, lds2) }
-    else if constexpr (NS == 2) DPF_P2(true, false, lds2)
-#undef DPF_P2
+    const dim3 grid2(grid.x, mj.rows + grid.y, form.split2 ? 2 : 1);
+    int rc2 = 0;
+    if (form.split2) rc2 = form.roles ? launch_pass2<NS, F16, false, true>(grid2, s, a, mj, count, dcanon_l, w)
+                                      : launch_pass2<NS, F16, false, false>(grid2, s, a, mj, count, dcanon_l, w);
+    else if constexpr (NS == 2) rc2 = launch_pass2<NS, F16, true, false>(grid2, s, a, mj, count, dcanon_l, w);
+    if (rc2) return rc2;
     const float *ubuf2 = w.ubuf + (size_t)B * 2 * N;                      // u_k comes in two planes (one per branch) either way
-    if (!fuse_env || last) {              // (fused: the next backward layer's pass 1 sums these partials; the last layer has none)
+    if (!fuse || last) {                  // (fused: the next backward layer's pass 1 sums these partials; the last layer has none)
         KScope ks(6, s);
         hipLaunchKernelGGL(tcolsum_kernel, dim3((2 * P2_J + 31) / 32), dim3(1024), 0, s, nblk, 2 * P2_J, w.part2, w.tot2, dcanon_l, P2_J);
     }
@@ -2383,49 +2399,40 @@ static int backward_layer(int B, int N, int mode, int ka, int kb, int wa, int wb
 }
 
 // Backward of the stack, layers in the reverse of the forward order.  The gradient that reaches layer l's p_out is
-// g_p(l) plus what the next layer passes down; g_p / g_mu / g_lv of a layer may be NULL (zero).  dp_in (B,3,N),
-// dcanon (L, T_LAYER) and dfm (L,[br][sub][B][64]) are fully overwritten; dp_tmp is a (B,3,N) scratch buffer.
+// g_p(l) plus what the next layer passes down; grad_of(which, l, lst) is layer l's gradient w.r.t. ps / mus / logvars
+// (which = 0 / 1 / 2; lst = B * 3 * N floats) and may be NULL (zero).  dp_in (B,3,N), dcanon (L, T_LAYER) and dfm
+// (L,[br][sub][B][64]) are fully overwritten; dp_tmp is a (B,3,N) scratch buffer.
 template <class GP>
 static int backward_stack(int n_layers, int B, int N, int mode, int precision, const int *meta_host, const float *tcanon,
                           const void *packed, const float *film, const float *stats, const float *p_in, const float *ps,
                           const float *mus, const float *logvars, GP &&grad_of, float *dp_in, float *dp_tmp, float *dcanon,
-                          float *dfm, float flow_eps, void *workspace, dpf_stream_t stream) {
-    if (n_layers <= 0 || B <= 0 || N <= 0 || !meta_host || !tcanon || !packed || !film || !stats || !p_in || !ps || !mus || !logvars ||
-        !dp_in || !dp_tmp || !dcanon || !dfm || !workspace)
-        return DPF_EINVAL;
-    if (mode != DPF_MODE_DIRECT && mode != DPF_MODE_INVERSE) return DPF_EINVAL;
-    const int ns = t_ns(precision);
-    if (!ns || B > 65535) return DPF_ENOSUP;
-    const size_t lst = (size_t)B * 3 * N, fls = dpf_flow_train_film_floats(B), fms = (size_t)4 * B * DPF_FLOW_F;
+                          float *dfm, float flow_eps, void *workspace, hipStream_t stream) {
+    StackCall c;
+    if (int rc = stack_open(n_layers, B, N, mode, precision, meta_host && tcanon && packed && film && stats && p_in && ps && mus &&
+                            logvars && dp_in && dp_tmp && dcanon && dfm && workspace, flow_eps, workspace, stream, &c))
+        return rc;
+    const size_t lst = c.lst;
     const float *chain = nullptr;
     int pass2_launches = 0;          // pass-2 launches of this call that carried role workgroups so far (their counter is monotonic over the call)
+    // no layer above the first one (has = 0), but pointers its pass 1 can load from unconditionally
+    const int l0 = mode == DPF_MODE_DIRECT ? n_layers - 1 : 0;
     PrevLayer pv = {};
-    {   // no layer above the first one (has = 0), but pointers its pass 1 can load from unconditionally
-        TWork w0;
-        carve(workspace, B, N, &w0);
-        const int l0 = mode == DPF_MODE_DIRECT ? n_layers - 1 : 0;
-        pv.tot = w0.tot2; pv.tcanon_l = tcanon + (size_t)l0 * T_LAYER; pv.stats_l = stats + (size_t)l0 * ST_LAYER;
-        pv.ka = 0; pv.kb = -1;
-    }
-    {   // the role workgroups' arrival counters start at zero (they are monotonic over the call).  A fill KERNEL: as a captured
-        // memset node the clear was not reliably ordered before the first pass-1 kernel of a replay (zero_fill.h)
-        TWork w;
-        carve(workspace, B, N, &w);
-        if (hipError_t e = dpf_zero_async(w.tickets, (size_t)(B + 16) * 4, (hipStream_t)stream); e != hipSuccess) return (int)e;
-    }
+    pv.tot = c.w.tot2; pv.tcanon_l = tcanon + (size_t)l0 * T_LAYER; pv.stats_l = stats + (size_t)l0 * ST_LAYER;
+    pv.ka = 0; pv.kb = -1;
+    // the role workgroups' arrival counters start at zero (they are monotonic over the call).  A fill KERNEL: as a captured
+    // memset node the clear was not reliably ordered before the first pass-1 kernel of a replay (zero_fill.h)
+    if (hipError_t e = dpf_zero_async(c.w.tickets, (size_t)(B + 16) * 4, stream); e != hipSuccess) return (int)e;
     for (int step = n_layers - 1; step >= 0; --step) {
         const int l = mode == DPF_MODE_DIRECT ? step : n_layers - 1 - step;
         const int lprev = mode == DPF_MODE_DIRECT ? step - 1 : n_layers - step;       // layer whose output fed layer l
         const float *pin = step == 0 ? p_in : ps + lprev * lst;
         float *out = (step & 1) ? dp_tmp : dp_in;                                      // step 0 writes dp_in
-        const int *m = meta_host + 4 * l;
-#define DPF_BWD(NSV, ...)                                                                                                 \
-    backward_layer<NSV, ##__VA_ARGS__>(B, N, mode, m[0], m[1], m[2], m[3], tcanon + (size_t)l * T_LAYER,                \
-                        (const uint8_t *)packed + (size_t)l * pt_bytes(NSV), film + l * fls, stats + (size_t)l * ST_LAYER, pin, \
-                        mus + l * lst, logvars + l * lst, grad_of(0, l), chain, grad_of(1, l), grad_of(2, l), out,       \
-                        dcanon + (size_t)l * T_LAYER, dfm + l * fms, flow_eps, workspace, (hipStream_t)stream, &pv, &pass2_launches, step == 0)
-        const int rc = precision == DPF_PREC_F16X3 ? DPF_BWD(2, true) : (ns == 2 ? DPF_BWD(2) : DPF_BWD(3));
-#undef DPF_BWD
+        const int rc = with_precision(precision, [&](auto ns, auto f16) {
+            return backward_layer<ns, f16>(c, meta_host + 4 * l, tcanon + (size_t)l * T_LAYER, (const uint8_t *)packed + (size_t)l * pt_bytes(ns),
+                                           film + l * c.fls, stats + (size_t)l * ST_LAYER, pin, mus + l * lst, logvars + l * lst,
+                                           grad_of(0, l, lst), chain, grad_of(1, l, lst), grad_of(2, l, lst), out,
+                                           dcanon + (size_t)l * T_LAYER, dfm + l * c.fms, &pv, &pass2_launches, step == 0);
+        });
         if (rc) return rc;
         chain = out;
     }
@@ -2439,24 +2446,18 @@ extern "C" int dpf_flow_train_backward(int n_layers, int B, int N, int mode, int
                                        const float *g_ps, const float *g_mus, const float *g_lvs, float *dp_in, float *dp_tmp,
                                        float *dcanon, float *dfm, float flow_eps, void *workspace, dpf_stream_t stream) {
     if (!g_ps) return DPF_EINVAL;
-    const size_t lst = (size_t)(B > 0 ? B : 0) * 3 * (N > 0 ? N : 0);
     const float *base[3] = {g_ps, g_mus, g_lvs};
     auto direct = [&](hipStream_t st) {
         return backward_stack(n_layers, B, N, mode, precision, meta_host, tcanon, packed, film, stats, p_in, ps, mus, logvars,
-                              [&](int which, int l) { return base[which] ? base[which] + l * lst : nullptr; }, dp_in, dp_tmp,
-                              dcanon, dfm, flow_eps, workspace, (dpf_stream_t)st);
+                              [&](int which, int l, size_t lst) { return base[which] ? base[which] + l * lst : nullptr; }, dp_in,
+                              dp_tmp, dcanon, dfm, flow_eps, workspace, st);
     };
     if (n_layers <= 0 || !meta_host) return direct((hipStream_t)stream);
     static GraphCache cache;
-    GraphKey k;
-    k.val(n_layers); k.val(B); k.val(N); k.val(mode); k.val(precision); k.add(meta_host, sizeof(int) * 4 * n_layers);
-    k.val(tcanon); k.val(packed); k.val(film); k.val(stats); k.val(p_in); k.val(ps); k.val(mus); k.val(logvars); k.val(g_ps);
-    k.val(g_mus); k.val(g_lvs);
-    k.val(dp_in); k.val(dp_tmp); k.val(dcanon); k.val(dfm); k.val(flow_eps); k.val(workspace);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    k.val(dev);
-    return cache.run(k, (hipStream_t)stream, direct);
+    return dpf_graph_call(cache, (hipStream_t)stream, direct, [&](GraphKey &k) {
+        k.vals(n_layers, B, N, mode, precision); k.add(meta_host, sizeof(int) * 4 * n_layers);
+        k.vals(tcanon, packed, film, stats, p_in, ps, mus, logvars, g_ps, g_mus, g_lvs, dp_in, dp_tmp, dcanon, dfm, flow_eps, workspace);
+    });
 }
 
 // The same with one (B,3,N) gradient pointer per layer and list: autograd hands the node a gradient per output
@@ -2471,27 +2472,23 @@ extern "C" int dpf_flow_train_backward_lists(int n_layers, int B, int N, int mod
     const float *const *tab[3] = {g_ps, g_mus, g_lvs};
     auto direct = [&](hipStream_t st) {
         return backward_stack(n_layers, B, N, mode, precision, meta_host, tcanon, packed, film, stats, p_in, ps, mus, logvars,
-                              [&](int which, int l) { return tab[which] ? tab[which][l] : nullptr; }, dp_in, dp_tmp, dcanon,
-                              dfm, flow_eps, workspace, (dpf_stream_t)st);
+                              [&](int which, int l, size_t) { return tab[which] ? tab[which][l] : nullptr; }, dp_in, dp_tmp, dcanon,
+                              dfm, flow_eps, workspace, st);
     };
     if (n_layers <= 0 || !meta_host) return direct((hipStream_t)stream);
     static GraphCache cache;
-    GraphKey k;
-    k.val(n_layers); k.val(B); k.val(N); k.val(mode); k.val(precision); k.add(meta_host, sizeof(int) * 4 * n_layers);
-    k.val(tcanon); k.val(packed); k.val(film); k.val(stats); k.val(p_in); k.val(ps); k.val(mus); k.val(logvars);
-    for (int w = 0; w < 3; ++w) {
-        const int present = tab[w] != nullptr;
-        k.val(present);
-        if (present) k.add(tab[w], sizeof(const float *) * n_layers);      // the per-layer gradient pointers themselves
-    }
-    k.val(dp_in); k.val(dp_tmp); k.val(dcanon); k.val(dfm); k.val(flow_eps); k.val(workspace);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    k.val(dev);
-    return cache.run(k, (hipStream_t)stream, direct);
+    return dpf_graph_call(cache, (hipStream_t)stream, direct, [&](GraphKey &k) {
+        k.vals(n_layers, B, N, mode, precision); k.add(meta_host, sizeof(int) * 4 * n_layers);
+        k.vals(tcanon, packed, film, stats, p_in, ps, mus, logvars);
+        for (int w = 0; w < 3; ++w) {
+            const int present = tab[w] != nullptr;
+            k.val(present);
+            if (present) k.add(tab[w], sizeof(const float *) * n_layers);      // the per-layer gradient pointers themselves
+        }
+        k.vals(dp_in, dp_tmp, dcanon, dfm, flow_eps, workspace);
+    });
 }
 
-// number of training-mode calls served by a graph replay so far in this process (csrc/graph_cache.h); diagnostics / tests
 // BatchNorm running statistics of a training step, all 8 L BatchNorm1d layers of the stack in one launch:
 //   running = (1 - momentum) * running + momentum * batch      (nn.BatchNorm1d; unbiased batch variance)
 // rows [0, 4L): the FiLM nets (batch statistics from dpf_film_train_forward or the caller's tensor ops), rows [4L, 8L): the

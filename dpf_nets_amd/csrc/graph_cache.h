@@ -51,6 +51,7 @@ struct GraphKey {
         bytes.insert(bytes.end(), b, b + n);
     }
     template <class T> void val(const T &v) { add(&v, sizeof(T)); }
+    template <class... T> void vals(const T &...v) { (val(v), ...); }
 };
 
 class GraphCache {
@@ -127,3 +128,15 @@ public:
         return (int)hipGraphLaunch(hit->exec, s);
     }
 };
+
+// A graph-cached entry in one call: fill(key) adds every scalar and pointer the launches depend on (and the bytes of any host
+// table they read), the current device is added here, then cache.run.  Each entry keeps a `static GraphCache` of its own.
+template <class F, class Fill>
+int dpf_graph_call(GraphCache &cache, hipStream_t s, F &&direct, Fill &&fill) {
+    GraphKey k;
+    fill(k);
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    k.val(dev);
+    return cache.run(k, s, direct);
+}

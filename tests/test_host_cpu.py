@@ -58,6 +58,25 @@ def test_approx_emd_workspace_sizes_are_pinned():
     assert h.dpf_pairwise_emd_workspace_bytes(0, 3, 4, 4) == 0 and h.dpf_pairwise_emd_workspace_bytes(3, 3, 4, 0) == 0
 
 
+def test_training_workspace_sizes_are_pinned():
+    """The training workspaces of the flow stack and the encoder are each laid out once (csrc/flow_train.hip carve,
+    csrc/encoder_train.hip t_carve) and allocated by the caller from these size queries.  The totals below were taken from the
+    library of commit cbea9aa, whose carve functions ran in two modes (size query / pointers); the queries are host-only.
+    Single point, the smoke and benchmark shapes, sizes off the tile, the largest batch."""
+    from dpf_nets_amd import _lib
+    h = _lib.lib()
+    flow = {(1, 1): 112128, (4, 256): 261376, (8, 2048): 2974720, (16, 2048): 5876992, (32, 2048): 11681536, (3, 100): 198656,
+            (2, 4097): 1593344, (65535, 33): 2598666496}
+    encoder = {(1, 1): 2524416, (4, 256): 10573312, (8, 2048): 142574080, (16, 2048): 283400960, (32, 2048): 565054720,
+               (3, 100): 5200640, (2, 4097): 73158656, (65535, 33): 32331017728}
+    for shape, want in flow.items():
+        assert h.dpf_flow_train_workspace_bytes(*shape) == want, shape
+    for shape, want in encoder.items():
+        assert h.dpf_encoder_train_workspace_bytes(*shape) == want, shape
+    for shape in ((0, 5), (5, 0), (-1, 5), (5, -1), (0, 0)):                          # empty or invalid: nothing to allocate
+        assert h.dpf_flow_train_workspace_bytes(*shape) == 0 and h.dpf_encoder_train_workspace_bytes(*shape) == 0
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     from dpf_nets_amd import _lib
     monkeypatch.setattr(_lib, "_LIB", None)
