@@ -126,9 +126,9 @@ __global__ __launch_bounds__(256) void pack_kernel(int G, const float *__restric
 // ===========================================================================
 // FiLM conditioner
 // ===========================================================================
-// fp32 conditioner weights, transposed at pack time so that the 64 output features are the
-// contiguous (lane) dimension: per (layer, branch, sub-net w|b):
-//   WT[G][64] | sc[64] sh[64] (eval BatchNorm folded: u*sc + sh) | W1T[64][64] | bf1[64]
+// fp32 conditioner weights, laid out at pack time so that a thread (= one output feature) reads four consecutive k of its
+// feature as one 16-byte load and a wave reads 1 KiB contiguous: per (layer, branch, sub-net w|b):
+//   WT[G/4][64][4] | sc[64] sh[64] (eval BatchNorm folded: u*sc + sh) | W1T[16][64][4] | bf1[64]
 // and per (layer, branch): s1[64] t1[64] (BN1, affine=False) w2a[64] w2b[64] (output SharedDot rows).
 __host__ __device__ constexpr int fw_sub_floats(int G) { return 64 * G + 128 + 4096 + 64; }
 __host__ __device__ constexpr size_t fw_total_floats(int L, int G) { return (size_t)L * 4 * fw_sub_floats(G) + (size_t)L * 2 * 320; }
@@ -142,7 +142,8 @@ __global__ __launch_bounds__(256) void pack_film_kernel(int L, int G, const floa
     const float *cf = cb + C_FILM + sub * c_film_floats(G);
     const float *Wf0 = cf, *bnf = cf + 64 * G, *Wf1 = bnf + 256, *bf1 = Wf1 + 4096;
     float *o = fw + (size_t)blockIdx.x * fw_sub_floats(G);
-    for (int idx = threadIdx.x; idx < 64 * G; idx += 256) o[idx] = Wf0[(idx & 63) * G + (idx >> 6)];
+    // element idx = ((k / 4) * 64 + feature) * 4 + k % 4
+    for (int idx = threadIdx.x; idx < 64 * G; idx += 256) o[idx] = Wf0[((idx >> 2) & 63) * G + (idx >> 8) * 4 + (idx & 3)];
     o += 64 * G;
     if (threadIdx.x < 64) {
         const int f = threadIdx.x;
@@ -151,7 +152,7 @@ __global__ __launch_bounds__(256) void pack_film_kernel(int L, int G, const floa
         o[64 + f] = bnf[64 + f] - bnf[128 + f] * sc;
         o[128 + 4096 + f] = bf1[f];
     }
-    for (int idx = threadIdx.x; idx < 4096; idx += 256) o[128 + idx] = Wf1[(idx & 63) * 64 + (idx >> 6)];
+    for (int idx = threadIdx.x; idx < 4096; idx += 256) o[128 + idx] = Wf1[((idx >> 2) & 63) * 64 + (idx >> 8) * 4 + (idx & 3)];
     if (sub == 0 && threadIdx.x < 64) {
         const int f = threadIdx.x;
         float *c = fw + (size_t)L * 4 * fw_sub_floats(G) + (size_t)(l * 2 + br) * 320;
@@ -165,118 +166,136 @@ __global__ __launch_bounds__(256) void pack_film_kernel(int L, int G, const floa
     }
 }
 
-constexpr int FILM_CLOUDS = 8;    // clouds per workgroup
+constexpr int FILM_CUS = 256;     // compute units of the part: the conditioner's sharding rule (dpf_flow_film) aims at one workgroup each
 
-// 512 threads = 2 sub-nets (w, b) x 64 output features x 4 K-quarters.  Each thread reduces ONE
-// quarter of the contraction for all 8 clouds, so its weight loads (coalesced: feature = lane)
-// are all issued up front -- the kernel is two global round trips and two LDS reductions deep.
-__global__ __launch_bounds__(512) void film_kernel(int L, int B, int G, const float *__restrict__ fw,
+// One workgroup = one (layer, branch) x C clouds; 512 threads = 2 sub-nets (w, b) x 4 K-quarters x 64 output features
+// (feature = lane).  What bounds it is the first linear: per cloud 2 x 64 x G FMAs, and one broadcast LDS read of g per four of
+// them -- so the clouds are spread over the chip (C = 1, 2 or 4 by the host's rule) instead of 8 to a workgroup, of which a
+// small batch filled only a few.  The weights cannot be spread the same way: every output needs the whole hidden vector, every
+// hidden feature the whole of g, and the fold mixes the two sub-nets per feature (D = FC / FA takes cw AND cb), so every
+// workgroup that writes a block pulls all of its (layer, branch)'s first-layer weights.
+// ONE global round trip deep: a thread requests its share of g, ALL its weights of both linears (32 NB k of the first) and every
+// per-feature constant before it waits for anything; the phases below wait with counted vmcnt.  FULL: G = 128 NB (the model's
+// G = 128 and G = 512), one batch, no bounds in the contraction; any other G goes through <1, false>, which guards every four k
+// and takes a further round trip per 128 of G.  Three barriers: g in LDS, hidden vector, second linear's partial sums.
+// Every output keeps the order of additions it has had since r02: each K-quarter is one fma chain in ascending k, the quarters
+// are summed q = 0..3 -- the blocks do not depend on C, on the cloud's place in the batch or on the grid.
+// Workgroup id = group * P + p, P = 2 L rounded up to 8: workgroups are dealt round-robin over the 8 XCDs, so all the workgroups
+// of one (layer, branch) share an L2 and its weights leave HBM once (ids p >= 2 L have nothing to do).
+template <int NB, bool FULL, int C>
+__global__ __launch_bounds__(512) void film_kernel(int L, int P, int B, int Gr, const float *__restrict__ fw,
                                                    const float *__restrict__ g, float *__restrict__ film, float flow_eps) {
+    static_assert(C == 1 || C == 2 || C == 4, "a K-quarter's threads finish one cloud each");
+    static_assert(FULL || NB == 1, "the guarded form is built for batches of 32 k");
+    constexpr int NG = FULL ? (C * 32 * NB + 511) / 512 : 4;          // 16-byte pieces of g per thread: C * G / 4 <= 512 * NG (G <= 2048)
+    const int G = FULL ? 128 * NB : Gr;
     extern __shared__ __attribute__((aligned(16))) float fsm[];
-    float *gs = fsm;                                  // [8][G]
-    float *part = fsm + FILM_CLOUDS * G;              // [2 sub][4 kq][8 clouds][64]
-    float *hid = part + 2 * 4 * FILM_CLOUDS * 64;     // [2][8][64]
-    float *cbx = hid + 2 * FILM_CLOUDS * 64;          // [8][64]
-    const int l = blockIdx.x >> 1, br = blockIdx.x & 1;
-    const int b0 = blockIdx.y * FILM_CLOUDS;
+    float *gs = fsm;                                  // [C][G]
+    float *part = fsm + C * G;                        // [2 sub][4 kq][C][64]   first linear's K-quarter sums
+    float *hid = part + 2 * 4 * C * 64;               // [2][C][64]
+    float *part2 = hid + 2 * C * 64;                  // [2][4][C][64]          second linear's
+    const int p = blockIdx.x % P;
+    if (p >= 2 * L) return;
+    const int l = p >> 1, br = p & 1;
+    const int b0 = (blockIdx.x / P) * C;
     const int tid = threadIdx.x, sub = tid >> 8, f = tid & 63, kq = (tid >> 6) & 3;
     const float *w = fw + (size_t)((l * 2 + br) * 2 + sub) * fw_sub_floats(G);
     const float *WT = w, *sc = w + 64 * G, *sh = sc + 64, *W1T = sh + 64, *bf1 = W1T + 4096;
-    for (int e = tid; e < FILM_CLOUDS * G / 4; e += 512) {            // g rows of this workgroup's clouds
-        const int row = e / (G / 4), c4 = (e % (G / 4)) * 4;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (b0 + row < B) v = *(const f32x4 *)(g + (size_t)(b0 + row) * G + c4);
-        *(f32x4 *)(gs + row * G + c4) = v;
+    // ---- every request of this thread, g first (loads return in order).  No load sits under a condition: a piece that is not
+    // needed is read from a clamped (valid) address and dropped, so nothing here waits or branches
+    f32x4 gq[NG];
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {                                    // g rows of this workgroup's clouds
+        const int e = min(tid + 512 * j, C * G / 4 - 1), row = min(b0 + e / (G / 4), B - 1), c4 = (e % (G / 4)) * 4;
+        gq[j] = *(const f32x4 *)(g + (size_t)row * G + c4);
     }
-    // every small per-feature constant is requested now: nothing below waits on a fresh global round trip
+    __builtin_amdgcn_sched_barrier(0);                                // ... and stay first when the scheduler has had its say
+    const int kspan = G / 4, k0 = kq * kspan;                         // G % 16 == 0
+    f32x4 wv[8 * NB];
+    auto request = [&](int kk) {                                      // 32 NB k of the first linear's weights, from k0 + kk
+#pragma unroll
+        for (int i = 0; i < 8 * NB; ++i) wv[i] = *(const f32x4 *)(WT + ((size_t)min((k0 + kk) / 4 + i, G / 4 - 1) * 64 + f) * 4);
+    };
+    request(0);
+    f32x4 w1[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) w1[i] = *(const f32x4 *)(W1T + ((kq * 4 + i) * 64 + f) * 4);           // second linear: k = 16 kq + 4 i ..
     const float *cst = fw + (size_t)L * 4 * fw_sub_floats(G) + (size_t)(l * 2 + br) * 320;
-    const float bn_a = sc[f], bn_d = sh[f], bias1 = bf1[f];
+    const float bn_a = sc[f], bn_d = sh[f];
+    const float bias_w = bf1[f - sub * fw_sub_floats(G)], bias_b = bf1[f + (1 - sub) * fw_sub_floats(G)];
     const float s1 = cst[f], t1 = cst[64 + f], w2a = cst[128 + f], w2b = cst[192 + f], b2v = cst[256 + (f & 1)];
     const float wsc = cst[258];                  // f16x3: 2^k of this branch's packed W1 (1 otherwise); w2a / w2b already carry 2^-k
-    float acc[FILM_CLOUDS];
 #pragma unroll
-    for (int c = 0; c < FILM_CLOUDS; ++c) acc[c] = 0.f;
-    const int kspan = G / 4, k0 = kq * kspan;                         // G % 16 == 0
-    for (int kk = 0; kk < kspan; kk += 32) {                          // u = g . Wf0^T        flows.py:34/41
-        float wv[32];
+    for (int j = 0; j < NG; ++j) {
+        const int e = tid + 512 * j;
+        if (e < C * G / 4) *(f32x4 *)(gs + e * 4) = b0 + e / (G / 4) < B ? gq[j] : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    __syncthreads();                                                  // gs visible; waits for g alone
 #pragma unroll
-        for (int i = 0; i < 32; ++i) wv[i] = kk + i < kspan ? WT[(size_t)(k0 + kk + i) * 64 + f] : 0.f;
-        if (kk == 0) __syncthreads();                                 // gs visible (loads above already in flight)
+    for (int j = 0; j < NG; ++j) asm volatile("" :: "v"(gq[j]));      // a use that every thread has: the request stays up there
+    float acc[C];
 #pragma unroll
-        for (int i = 0; i < 32; i += 4) {
-            if (kk + i < kspan) {
+    for (int c = 0; c < C; ++c) acc[c] = 0.f;
+    auto contract = [&](int kk) {                                     // u = g . Wf0^T        flows.py:34/41
 #pragma unroll
-                for (int c = 0; c < FILM_CLOUDS; ++c) {
-                    const f32x4 x = *(const f32x4 *)(gs + c * G + k0 + kk + i);
+        for (int i = 0; i < 8 * NB; ++i) {
+            if (FULL || kk + 4 * i < kspan) {
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    const f32x4 x = *(const f32x4 *)(gs + c * G + k0 + kk + 4 * i);
                     // explicit fma chain: the same bits for a cloud wherever it sits in the batch
-                    acc[c] = __builtin_fmaf(wv[i + 3], x.w, __builtin_fmaf(wv[i + 2], x.z, __builtin_fmaf(wv[i + 1], x.y, __builtin_fmaf(wv[i], x.x, acc[c]))));
+                    acc[c] = __builtin_fmaf(wv[i].w, x.w, __builtin_fmaf(wv[i].z, x.z, __builtin_fmaf(wv[i].y, x.y, __builtin_fmaf(wv[i].x, x.x, acc[c]))));
                 }
             }
         }
-    }
-    float w1[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) w1[i] = W1T[(kq * 16 + i) * 64 + f];  // second layer's weights: in flight early
-#pragma unroll
-    for (int c = 0; c < FILM_CLOUDS; ++c) part[((sub * 4 + kq) * FILM_CLOUDS + c) * 64 + f] = acc[c];
-    __syncthreads();
-    {   // BatchNorm1d over the batch dim in eval mode (flows.py:35/42), then Swish (layers.py:9-10)
-        const float a = bn_a, d = bn_d;
-#pragma unroll
-        for (int cc = 0; cc < 2; ++cc) {
-            const int c = kq * 2 + cc;
-            float u = 0.f;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) u += part[((sub * 4 + q) * FILM_CLOUDS + c) * 64 + f];
-            u = u * a + d;
-            hid[(sub * FILM_CLOUDS + c) * 64 + f] = u / (1.0f + expf(-u));
+    };
+    contract(0);
+    if (!FULL)
+        for (int kk = 32; kk < kspan; kk += 32) {                     // further batches, a round trip each
+            request(kk);
+            contract(kk);
         }
+#pragma unroll
+    for (int c = 0; c < C; ++c) part[((sub * 4 + kq) * C + c) * 64 + f] = acc[c];
+    __syncthreads();
+    if (kq < C) {   // BatchNorm1d over the batch dim in eval mode (flows.py:35/42), then Swish (layers.py:9-10)
+        const float a = bn_a, d = bn_d;
+        const int c = kq;
+        float u = 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) u += part[((sub * 4 + q) * C + c) * 64 + f];
+        u = u * a + d;
+        hid[(sub * C + c) * 64 + f] = u / (1.0f + expf(-u));
     }
     __syncthreads();
 #pragma unroll
-    for (int c = 0; c < FILM_CLOUDS; ++c) {                           // Linear(F, F)          flows.py:37/44
-        const float *h0 = hid + (sub * FILM_CLOUDS + c) * 64 + kq * 16;
+    for (int c = 0; c < C; ++c) {                                     // Linear(F, F)          flows.py:37/44
+        const float *h0 = hid + (sub * C + c) * 64 + kq * 16;
         float a2 = 0.f;
 #pragma unroll
-        for (int i = 0; i < 16; i += 4) {
-            const f32x4 x = *(const f32x4 *)(h0 + i);
-            a2 = __builtin_fmaf(w1[i + 3], x.w, __builtin_fmaf(w1[i + 2], x.z, __builtin_fmaf(w1[i + 1], x.y, __builtin_fmaf(w1[i], x.x, a2))));
+        for (int i = 0; i < 4; ++i) {
+            const f32x4 x = *(const f32x4 *)(h0 + 4 * i);
+            a2 = __builtin_fmaf(w1[i].w, x.w, __builtin_fmaf(w1[i].z, x.z, __builtin_fmaf(w1[i].y, x.y, __builtin_fmaf(w1[i].x, x.x, a2))));
         }
-        acc[c] = a2;
-    }
-    __syncthreads();                                                  // everyone is done reading part (phase 1)
-#pragma unroll
-    for (int c = 0; c < FILM_CLOUDS; ++c) part[((sub * 4 + kq) * FILM_CLOUDS + c) * 64 + f] = acc[c];
-    __syncthreads();
-    float v[2];
-    {
-        const float bias = bias1;
-#pragma unroll
-        for (int cc = 0; cc < 2; ++cc) {
-            const int c = kq * 2 + cc;
-            float t = bias;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) t += part[((sub * 4 + q) * FILM_CLOUDS + c) * 64 + f];
-            v[cc] = t;
-            if (sub == 1) cbx[c * 64 + f] = t;
-        }
+        part2[((sub * 4 + kq) * C + c) * 64 + f] = a2;
     }
     __syncthreads();
-    if (sub == 1) return;
+    const int c = kq, b = b0 + c;
+    if (sub == 1 || c >= C || b >= B) return;
+    float v = bias_w, cbx = bias_b;                                   // cw and cb of (cloud c, feature f)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v += part2[(q * C + c) * 64 + f];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) cbx += part2[((4 + q) * C + c) * 64 + f];
     // fold FiLM (flows.py:100-101) with BN1 (affine=False, :30/65) and the output SharedDot (:49/84):
     //   relu((eps+e^cw) * BN1(h1) + cb) = FA * relu(h1 + FC/FA),  FA = (eps+e^cw)/sqrt(rv1+eps_bn) > 0
-#pragma unroll
-    for (int cc = 0; cc < 2; ++cc) {
-        const int c = kq * 2 + cc, b = b0 + c;
-        if (b >= B) continue;
-        const float a = flow_eps + expf(v[cc]);
-        const float FA = a * s1, FC = a * t1 + cbx[c * 64 + f];
-        float *o = film + ((size_t)l * B + b) * (FILM_BYTES / 4) + br * FILM_BR_FLOATS;
-        o[f] = (FC / FA) * wsc;
-        o[64 + f] = w2a * FA;
-        o[128 + f] = w2b * FA;
-        if (f < 2) film[((size_t)l * B + b) * (FILM_BYTES / 4) + FILM_B2_OFF + br * 2 + f] = b2v;
-    }
+    const float a = flow_eps + expf(v);
+    const float FA = a * s1, FC = a * t1 + cbx;
+    float *o = film + ((size_t)l * B + b) * (FILM_BYTES / 4) + br * FILM_BR_FLOATS;
+    o[f] = (FC / FA) * wsc;
+    o[64 + f] = w2a * FA;
+    o[128 + f] = w2b * FA;
+    if (f < 2) film[((size_t)l * B + b) * (FILM_BYTES / 4) + FILM_B2_OFF + br * 2 + f] = b2v;
 }
 
 // ===========================================================================
@@ -1015,12 +1034,18 @@ extern "C" int dpf_flow_film(int n_layers, int B, int G, int precision, const vo
     if (!packed || !g || !film) return DPF_EINVAL;
     if (G % 16 != 0 || G > 2048) return DPF_ENOSUP;
     const float *fw = (const float *)((const uint8_t *)packed + packed_frag_bytes(n_layers, precision));
-    const int lds = (FILM_CLOUDS * G + (2 * 4 + 2 + 1) * FILM_CLOUDS * 64) * (int)sizeof(float);
-    static LdsLimit film_limit;
-    if (lds > 65536)
-        if (hipError_t e = film_limit.ensure((const void *)film_kernel, lds); e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(film_kernel, dim3(n_layers * 2, (B + FILM_CLOUDS - 1) / FILM_CLOUDS), dim3(512), lds,
-                       (hipStream_t)stream, n_layers, B, G, fw, g, film, flow_eps);
+    // sharding, from the shape alone: the fewest clouds per workgroup (1, 2, 4) at which the grid does not exceed one workgroup
+    // per compute unit -- fewer clouds is less arithmetic per workgroup, a second workgroup on a compute unit is a second pull of
+    // the weights through the same L1 -- and 4 beyond that
+    const int C = 2 * n_layers * B <= FILM_CUS ? 1 : 2 * n_layers * ((B + 1) / 2) <= FILM_CUS ? 2 : 4;
+    const int P = (2 * n_layers + 7) & ~7;
+    const int lds = C * (G + (2 * 4 + 2 + 2 * 4) * 64) * (int)sizeof(float);       // <= 50 KiB (G <= 2048)
+    const dim3 grid(P * ((B + C - 1) / C));
+#define DPF_FILM(NB, FULL, C_) hipLaunchKernelGGL((film_kernel<NB, FULL, C_>), grid, dim3(512), lds, (hipStream_t)stream, n_layers, P, B, G, fw, g, film, flow_eps)
+#define DPF_FILM_C(NB, FULL) { if (C == 1) DPF_FILM(NB, FULL, 1); else if (C == 2) DPF_FILM(NB, FULL, 2); else DPF_FILM(NB, FULL, 4); }
+    if (G == 128) DPF_FILM_C(1, true) else if (G == 512) DPF_FILM_C(4, true) else DPF_FILM_C(1, false)
+#undef DPF_FILM_C
+#undef DPF_FILM
     return (int)hipGetLastError();
 }
 
