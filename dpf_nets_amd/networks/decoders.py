@@ -11,10 +11,11 @@ import torch.nn as nn
 
 from .flows import CondRealNVPFlow3DTriple, _needs_autograd, use_hip_training, train_stack, stack_spec
 from .flowlist import FlowList
+from .layers import PackedWeights
 from .engine import FlowStack
 
 
-class LocalCondRNVPDecoder(nn.Module):
+class LocalCondRNVPDecoder(PackedWeights, nn.Module):
     def __init__(self, n_flows, f_n_features, g_n_features, weight_std=0.01):
         super().__init__()
         self.n_flows, self.f_n_features, self.g_n_features = n_flows, f_n_features, g_n_features
@@ -22,32 +23,15 @@ class LocalCondRNVPDecoder(nn.Module):
         self.flows = nn.ModuleList([
             CondRealNVPFlow3DTriple(f_n_features, g_n_features, weight_std=weight_std, pattern=i % 2)
             for i in range(n_flows)])
-        object.__setattr__(self, "_stack", None)
         self.precision = None          # None -> engine.DEFAULT_PRECISION ("f16x3")
         self.materialize_lists = True  # False: skip the 3 x L per-layer tensors (lists then hold the final layer only)
-        self.register_load_state_dict_post_hook(lambda m, keys: m.invalidate_packed())
 
     def coupling_layers(self):
         """All 3*n_flows CondRealNVPFlow3D modules in DIRECT order."""
         return [lyr for tri in self.flows for lyr in tri.layers()]
 
-    def invalidate_packed(self):
-        if self._stack is not None:
-            self._stack.invalidate()
-
-    def train(self, mode=True):
-        if mode != self.training:
-            self.invalidate_packed()
-        return super().train(mode)
-
-    def _apply(self, fn, *a, **kw):
-        self.invalidate_packed()
-        return super()._apply(fn, *a, **kw)
-
     def stack(self):
-        if self._stack is None:
-            object.__setattr__(self, "_stack", FlowStack(self.coupling_layers()))
-        return self._stack
+        return self.packed_stack(lambda: FlowStack(self.coupling_layers()))
 
     def flatten_parameters(self):
         """Opt-in (extension; DPF_TRAIN_FLAT=1 does it on the first training step): move every parameter and

@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from .._lib import lib, check, current_stream, PREC
-from .layers import SharedDot
+from .layers import SharedDot, weight_state
 
 _HIP_ARCH = (3, 64, (128, 256, 512))
 
@@ -259,7 +259,7 @@ class PointNetCloudEncoder(nn.Module):
     def _packed(self, dev):
         """bf16 MFMA fragments of the BatchNorm-folded weights, cached per (weight version, precision, device)"""
         ts = self._layer_tensors()
-        state = tuple((t._version, t.data_ptr()) for t in ts)
+        state = weight_state(ts)
         key = (self.precision, str(dev))
         hit = self._pack_cache.get(key)
         if hit is not None and hit[0] == state:

@@ -12,6 +12,7 @@ import os
 import torch
 
 from .._lib import lib, check, current_stream, PREC, MODE
+from .layers import weight_state
 
 # "f16x3" (default): W1 and the hidden activations as fp16 hi + lo parts, three MFMA products -- ~5e-7 of the reference
 # (fp32-class), and the cheapest split on the VALU; "bf16x3": the same with bf16 parts (~7e-6; no fp16 range limit);
@@ -79,11 +80,8 @@ class FlowStack:
         self._canon = None
         self._packed = {}
 
-    def _sentinel(self):
-        return tuple((t._version, t.data_ptr()) for t in self._sentinels)
-
     def _check_fresh(self):
-        s = self._sentinel()
+        s = weight_state(self._sentinels)
         if s != self._sentinel_state:
             self.invalidate()
             self._sentinel_state = s

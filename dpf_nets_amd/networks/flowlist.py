@@ -10,25 +10,42 @@ remembers the layer-sum the kernel accumulated in registers."""
 from collections.abc import Sequence
 
 
+def tag_layer_sum(views, total):
+    """Tag the tensors of `views` as one stack's whole list, and the last of them with their layer-sum `total` (None: not
+    at hand), so that a python list that ENDS with them -- `[prior] + views` -- can still be recognised (tagged_tail).
+    The tags hold no reference back to a list: no cycles.  Returns `views`."""
+    token = object()
+    for i, v in enumerate(views):
+        v._dpf_pos = (token, i)
+    if total is not None and views:
+        views[-1]._dpf_total = (token, len(views), total)
+    return views
+
+
+def tagged_tail(logvars):
+    """(k, total) when the last k entries of `logvars` are one stack's whole list whose layer-sum is `total`, else None."""
+    n = len(logvars)
+    tag = getattr(logvars[-1], "_dpf_total", None) if n else None
+    if tag is not None:
+        token, k, total = tag
+        if n >= k and all(getattr(logvars[n - k + i], "_dpf_pos", None) == (token, i) for i in range(k)):
+            return k, total
+    return None
+
+
 class FlowList(Sequence):
     def __init__(self, buf, total=None):
         self._buf = buf            # (L, B, 3, N)
         self._total = total        # (B, 3, N) = sum over L from the kernel, or None
         self._views = None
-        self._token = object()
 
     def __len__(self):
         return self._buf.shape[0]
 
     def views(self):
         if self._views is None:
-            self._views = list(self._buf.unbind(0))
-            # tag the views so that a python list built by `[prior] + flowlist` can still be
-            # recognised by losses.total_logvar (no reference back to self: no cycles)
-            for i, v in enumerate(self._views):
-                v._dpf_pos = (self._token, i)
-            if self._total is not None and self._views:
-                self._views[-1]._dpf_total = (self._token, len(self._views), self._total)
+            # tagged: a python list built by `[prior] + flowlist` is still recognised by losses.total_logvar
+            self._views = tag_layer_sum(list(self._buf.unbind(0)), self._total)
         return self._views
 
     def __getitem__(self, i):

@@ -18,7 +18,7 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 
-from .layers import SharedDot, Swish
+from .layers import SharedDot, Swish, PackedWeights, EvalModeAutogradWarning, _needs_autograd   # noqa: F401  (re-exported)
 from .engine import FlowStack
 
 TRAIN_IMPL = os.environ.get("DPF_TRAIN_IMPL", "hip")
@@ -51,27 +51,7 @@ def train_stack(owner, layers, p, g, mode, allow_flat=False):
     return run_training_stack(spec, p, g, mode)
 
 
-class EvalModeAutogradWarning(RuntimeWarning):
-    """An eval()-mode module was called under autograd: the call is served by PyTorch tensor operations, not by the HIP kernels."""
-
-
-def _needs_autograd(*tensors):
-    """True when an eval()-mode call must stay differentiable with respect to its INPUTS (the reference's
-    CondRealNVPFlow3D.forward is: flows.py:95-117).  The fused HIP stacks have a backward pass for training-mode BatchNorm only
-    (csrc/flow_train.hip); an eval-mode call under autograd therefore runs the reference's op sequence on ATen (~30 kernels per
-    layer) -- correct, differentiable, and some 50x slower than the fused stack.  That is a SECOND backend behind forward(), so it
-    is loud: one EvalModeAutogradWarning per call site.  The reference's own loops never take it
-    (evaluating.py:58-59 runs under no_grad; training.py:37-56 in train() mode)."""
-    need = torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
-    if need:
-        import warnings
-        warnings.warn("eval()-mode flow called with inputs that require grad: served by PyTorch tensor operations (differentiable, "
-                      "~30 ATen kernels per coupling layer), not by the fused HIP stack; call under torch.no_grad() for the HIP "
-                      "path, or in train() mode for the HIP training kernels", EvalModeAutogradWarning, stacklevel=3)
-    return need
-
-
-class CondRealNVPFlow3D(nn.Module):
+class CondRealNVPFlow3D(PackedWeights, nn.Module):
     def __init__(self, f_n_features, g_n_features, weight_std=0.01, warp_inds=[0],
                  centered_translation=False, eps=1e-6):
         super().__init__()
@@ -108,23 +88,7 @@ class CondRealNVPFlow3D(nn.Module):
                              getattr(self, "T_%s_1" % br)[-1]):
                     last.weight.normal_(std=weight_std)
                     last.bias.zero_()
-        object.__setattr__(self, "_stack", None)
         self.precision = None                                      # None -> engine.DEFAULT_PRECISION
-        self.register_load_state_dict_post_hook(lambda m, keys: m.invalidate_packed())
-
-    # -- packed-weight cache invalidation --------------------------------------
-    def invalidate_packed(self):
-        if self._stack is not None:
-            self._stack.invalidate()
-
-    def train(self, mode=True):
-        if mode != self.training:
-            self.invalidate_packed()
-        return super().train(mode)
-
-    def _apply(self, fn, *a, **kw):
-        self.invalidate_packed()
-        return super()._apply(fn, *a, **kw)
 
     # -- the two paths -----------------------------------------------------------
     def _conditioner(self, br, x, g):
@@ -156,9 +120,7 @@ class CondRealNVPFlow3D(nn.Module):
             return ps[0], mus[0], lvs[0]
         if self.training or _needs_autograd(p, g):
             return self.forward_torch(p, g, mode)
-        if self._stack is None:
-            object.__setattr__(self, "_stack", FlowStack([self]))
-        p_out, _, ps, mus, lvs = self._stack.run(p, g, mode, self.precision, want_lists=True)
+        p_out, _, ps, mus, lvs = self.packed_stack(lambda: FlowStack([self])).run(p, g, mode, self.precision, want_lists=True)
         return p_out, mus[0], lvs[0]
 
 

@@ -1,9 +1,70 @@
 """SharedDot / Swish with the reference's parameter names, shapes and init
 (lib/networks/layers.py:5-45).  These modules carry the weights (state-dict
 compatibility) and serve the training-mode path; in eval mode the coupling
-layers read the weights out of them and run the fused HIP stack instead."""
+layers read the weights out of them and run the fused HIP stack instead.
+
+Also what every flow module shares around that switch: the packed-weight cache's invalidation (PackedWeights,
+weight_state) and the rule that sends an eval-mode call under autograd to tensor operations (_needs_autograd)."""
+import warnings
+
 import torch
 import torch.nn as nn
+
+
+class EvalModeAutogradWarning(RuntimeWarning):
+    """An eval()-mode module was called under autograd: the call is served by PyTorch tensor operations, not by the HIP kernels."""
+
+
+def _needs_autograd(*tensors):
+    """True when an eval()-mode call must stay differentiable with respect to its INPUTS (the reference's
+    CondRealNVPFlow3D.forward is: flows.py:95-117).  The fused HIP stacks have a backward pass for training-mode BatchNorm only
+    (csrc/flow_train.hip); an eval-mode call under autograd therefore runs the reference's op sequence on ATen (~30 kernels per
+    layer) -- correct, differentiable, and some 50x slower than the fused stack.  That is a SECOND backend behind forward(), so it
+    is loud: one EvalModeAutogradWarning per call site.  The reference's own loops never take it
+    (evaluating.py:58-59 runs under no_grad; training.py:37-56 in train() mode)."""
+    need = torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+    if need:
+        warnings.warn("eval()-mode flow called with inputs that require grad: served by PyTorch tensor operations (differentiable, "
+                      "~30 ATen kernels per coupling layer), not by the fused HIP stack; call under torch.no_grad() for the HIP "
+                      "path, or in train() mode for the HIP training kernels", EvalModeAutogradWarning, stacklevel=3)
+    return need
+
+
+def weight_state(tensors):
+    """Fingerprint of the weights a packed copy was built from: in-place edits bump `_version`, a re-assigned `.data` moves."""
+    return tuple((t._version, t.data_ptr()) for t in tensors)
+
+
+class PackedWeights:
+    """Mixin of the flow modules: `_stack` holds the module's fused eval-mode stack (engine.FlowStack / prior_flows.GPriorStack)
+    in the instance __dict__, outside nn.Module's registries.  Its packed weights are rebuilt after anything that may have
+    changed the parameters behind the version counters' back -- optimizers update through `.data` -- i.e. on every
+    train()/eval() switch, load_state_dict, .to()/.cuda()/.float(); in between, the stack's sentinels (weight_state) catch
+    ordinary in-place edits."""
+    _stack = None
+
+    def packed_stack(self, build):
+        """The module's stack, built by `build()` on first use."""
+        if self._stack is None:
+            self.__dict__["_stack"] = build()
+        return self._stack
+
+    def invalidate_packed(self):
+        if self._stack is not None:
+            self._stack.invalidate()
+
+    def train(self, mode=True):
+        if mode != self.training:
+            self.invalidate_packed()
+        return super().train(mode)
+
+    def _apply(self, fn, *a, **kw):
+        self.invalidate_packed()
+        return super()._apply(fn, *a, **kw)
+
+    def _load_from_state_dict(self, *a, **kw):
+        self.invalidate_packed()
+        return super()._load_from_state_dict(*a, **kw)
 
 
 class Swish(nn.Module):

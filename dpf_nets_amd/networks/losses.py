@@ -11,52 +11,55 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .flowlist import FlowList
+from .flowlist import FlowList, tagged_tail
 
 
 def total_logvar(logvars):
     """sum(logvars) for a plain list, a FlowList, or `[prior...] + FlowList` lists."""
     if isinstance(logvars, FlowList):
         return logvars.total()
-    tag = getattr(logvars[-1], "_dpf_total", None) if len(logvars) else None
-    if tag is not None:
-        token, k, total = tag
-        if len(logvars) >= k and all(
-                getattr(logvars[len(logvars) - k + i], "_dpf_pos", None) == (token, i) for i in range(k)):
-            head = logvars[:len(logvars) - k]
-            return (sum(head) + total) if len(head) else total
-    return sum(logvars)
+    tail = tagged_tail(logvars)
+    if tail is None:
+        return sum(logvars)
+    k, total = tail
+    head = logvars[:len(logvars) - k]
+    return (sum(head) + total) if len(head) else total
 
 
 def _flow_total(logvars):
-    """(total of logvars[1:], True) when logvars is `[base] + <the fused stack's list>` and the stack left its layer-sum."""
-    if len(logvars) < 2:
-        return None, False
-    tag = getattr(logvars[-1], "_dpf_total", None)
-    if tag is None:
-        return None, False
-    token, k, total = tag
-    if len(logvars) == k + 1 and all(getattr(logvars[1 + i], "_dpf_pos", None) == (token, i) for i in range(k)):
-        return total, True
-    return None, False
+    """The total of logvars[1:] when logvars is `[base] + <the fused stack's list>` and the stack left its layer-sum, else None."""
+    tail = tagged_tail(logvars)
+    return tail[1] if tail is not None and len(logvars) == tail[0] + 1 else None
+
+
+def _nll_fusable(s0, mu0, lv0):
+    """What csrc/nll.hip takes: a (B,C,N) fp32 CUDA sample and fp32 base-distribution tensors (or expansions) of its shape."""
+    return s0.is_cuda and s0.dim() == 3 and s0.dtype == torch.float32 and mu0.shape == s0.shape and lv0.shape == s0.shape and \
+        mu0.dtype == lv0.dtype == torch.float32
+
+
+def _nll_launch(s0, mu0, lv0, total):
+    """dpf_pointflow_nll: one pass over the contiguous s0 and the stack's layer-sum of log-variances, the base distribution's
+    stride-0 expansions read through their strides (csrc/nll.hip) -> the loss, a 0-d tensor."""
+    from .._lib import lib, check, current_stream
+    B, C, N = s0.shape
+    out = torch.empty((), dtype=torch.float32, device=s0.device)
+    ws = torch.empty(lib().dpf_pointflow_nll_workspace_floats(), dtype=torch.float32, device=s0.device)
+    with torch.cuda.device(s0.device):
+        check(lib().dpf_pointflow_nll(B, C, N, s0.data_ptr(), mu0.data_ptr(), *mu0.stride(), lv0.data_ptr(), *lv0.stride(),
+                                      total.data_ptr(), ws.data_ptr(), out.data_ptr(), current_stream()), "pointflow_nll")
+    return out
 
 
 class _PointFlowNLLNode(torch.autograd.Function):
     """losses.py:11-15 as ONE autograd node over HIP kernels (training step): forward =
-    dpf_pointflow_nll (one pass over s0 and the stack's layer-sum of log-variances, base distribution through its strides),
-    backward = dpf_pointflow_nll_backward (one launch: d s0, the constant d sum_lv, and d mu0 / d lv0 only if the base
-    distribution is learned)."""
+    dpf_pointflow_nll (_nll_launch), backward = dpf_pointflow_nll_backward (one launch: d s0, the constant d sum_lv, and
+    d mu0 / d lv0 only if the base distribution is learned)."""
 
     @staticmethod
     def forward(ctx, s0, mu0, lv0, total):
-        from .._lib import lib, check, current_stream
-        B, C, N = s0.shape
         s0c = s0.contiguous()
-        out = torch.empty((), dtype=torch.float32, device=s0.device)
-        ws = torch.empty(lib().dpf_pointflow_nll_workspace_floats(), dtype=torch.float32, device=s0.device)
-        with torch.cuda.device(s0.device):
-            check(lib().dpf_pointflow_nll(B, C, N, s0c.data_ptr(), mu0.data_ptr(), *mu0.stride(), lv0.data_ptr(), *lv0.stride(),
-                                          total.data_ptr(), ws.data_ptr(), out.data_ptr(), current_stream()), "pointflow_nll")
+        out = _nll_launch(s0c, mu0, lv0, total)
         ctx.save_for_backward(s0c, mu0, lv0)
         return out
 
@@ -82,29 +85,15 @@ class _PointFlowNLLNode(torch.autograd.Function):
 class PointFlowNLL(nn.Module):
     def forward(self, samples, mus, logvars):
         s0, mu0, lv0 = samples[0], mus[0], logvars[0]
-        # training step on CUDA tensors: the stack's layer-sum of log-variances is at hand -> one fused node
-        if s0.is_cuda and s0.dim() == 3 and s0.dtype == torch.float32 and mu0.shape == s0.shape and lv0.shape == s0.shape and \
-                mu0.dtype == lv0.dtype == torch.float32 and torch.is_grad_enabled() and \
-                (s0.requires_grad or mu0.requires_grad or lv0.requires_grad):
-            total, ok = _flow_total(logvars)
-            if ok and total.dtype == torch.float32 and total.shape == s0.shape:
+        total = _flow_total(logvars) if _nll_fusable(s0, mu0, lv0) else None
+        if total is None:
+            pass
+        elif torch.is_grad_enabled() and (s0.requires_grad or mu0.requires_grad or lv0.requires_grad):
+            # training step: the stack's layer-sum of log-variances is at hand -> one fused node
+            if total.dtype == torch.float32 and total.shape == s0.shape:
                 return _PointFlowNLLNode.apply(s0, mu0, lv0, total.contiguous())
-        # evaluation (CUDA tensors, nothing to differentiate): one pass over s0 and the kernel's sum of log-variances, the
-        # base distribution's stride-0 expansions read through their strides (csrc/nll.hip)
-        if s0.is_cuda and s0.dim() == 3 and s0.dtype == torch.float32 and mu0.shape == s0.shape and lv0.shape == s0.shape and \
-                mu0.dtype == lv0.dtype == torch.float32 and \
-                not (torch.is_grad_enabled() and (s0.requires_grad or mu0.requires_grad or lv0.requires_grad)):
-            total, ok = _flow_total(logvars)
-            if ok and total.is_contiguous() and not (torch.is_grad_enabled() and total.requires_grad):
-                from .._lib import lib, check, current_stream
-                B, C, N = s0.shape
-                s0 = s0.contiguous()
-                out = torch.empty((), dtype=torch.float32, device=s0.device)
-                ws = torch.empty(lib().dpf_pointflow_nll_workspace_floats(), dtype=torch.float32, device=s0.device)
-                with torch.cuda.device(s0.device):
-                    check(lib().dpf_pointflow_nll(B, C, N, s0.data_ptr(), mu0.data_ptr(), *mu0.stride(), lv0.data_ptr(), *lv0.stride(),
-                                                  total.data_ptr(), ws.data_ptr(), out.data_ptr(), current_stream()), "pointflow_nll")
-                return out
+        elif total.is_contiguous() and not (torch.is_grad_enabled() and total.requires_grad):
+            return _nll_launch(s0.contiguous(), mu0, lv0, total)        # evaluation: nothing to differentiate
         tot = total_logvar(logvars) + (s0 - mu0) ** 2 / torch.exp(lv0)
         return 0.5 * (tot.sum() / s0.shape[0] + math.log(2.0 * math.pi) * s0.shape[1] * s0.shape[2])
 

@@ -98,7 +98,7 @@ class Adam(Optimizer):
         fs = {"flat_p": store.flat_p, "buf": {}, "views": {}}
         for n in names:
             buf = torch.zeros_like(store.flat_p)
-            views = [buf[v.data_ptr() // 4 - store.flat_p.data_ptr() // 4:][:v.numel()].view(v.shape) for v in store.pviews]
+            views = store.views_of(buf)
             old = [self.state[p].get(n) if p in self.state else None for p in store.params]
             if any(o is not None for o in old):
                 with torch.no_grad():
@@ -152,8 +152,7 @@ class Adam(Optimizer):
             stores, rest = self._split_group(group)
             others = list(rest)
             for store in stores:
-                ps, gv, mid = store.params, store.gviews, len(store.params) // 2
-                if store.attached() and ps[0].grad is gv[0] and ps[mid].grad is gv[mid] and ps[-1].grad is gv[-1]:
+                if store.attached() and store.grads_attached():
                     store.flat_g.zero_()
                     store.grad_written = not set_to_none
                 else:
@@ -169,6 +168,17 @@ class Adam(Optimizer):
                     else:
                         p.grad.requires_grad_(False)
                     p.grad.zero_()
+
+    def _step_flat(self, store, fs, lr, beta1, beta2, eps, wd, amsgrad):
+        """One more step of a whole store (all of its step counters agree): the counters, then the update of the flat buffers."""
+        pst, buf = fs["pstates"], fs["buf"]
+        step = pst[0]["step"] + 1
+        for st in pst:
+            st["step"] = step
+        max_sq = buf["max_exp_avg_sq"] if amsgrad else None
+        if not self._update_flat(store.flat_p, store.flat_g, buf["exp_avg"], buf["exp_avg_sq"], max_sq, step, lr, beta1, beta2, eps, wd, amsgrad):
+            self._update([store.flat_p], [store.flat_g], [buf["exp_avg"]], [buf["exp_avg_sq"]], [max_sq] if amsgrad else None,
+                         step, lr, beta1, beta2, eps, wd, amsgrad)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -186,25 +196,15 @@ class Adam(Optimizer):
             stores, rest = self._split_group(group)
             general = list(rest)
             for store in stores:
-                done = False
-                if store.attached():
-                    ps, gv, mid = store.params, store.gviews, len(store.params) // 2
-                    if ps[0].grad is gv[0] and ps[mid].grad is gv[mid] and ps[-1].grad is gv[-1]:
-                        if not getattr(store, "grad_written", True):           # zero_grad(set_to_none=True) and nothing since: "grad is None"
-                            continue
-                        fs = self._flat_state(store, amsgrad)
-                        pst = fs["pstates"]
-                        if pst[0]["step"] == pst[mid]["step"] == pst[-1]["step"]:
-                            step = pst[0]["step"] + 1
-                            for st in pst:
-                                st["step"] = step
-                            if not self._update_flat(store.flat_p, store.flat_g, fs["buf"]["exp_avg"], fs["buf"]["exp_avg_sq"],
-                                                     fs["buf"]["max_exp_avg_sq"] if amsgrad else None, step, lr, beta1, beta2, eps, wd, amsgrad):
-                                self._update([store.flat_p], [store.flat_g], [fs["buf"]["exp_avg"]], [fs["buf"]["exp_avg_sq"]],
-                                             [fs["buf"]["max_exp_avg_sq"]] if amsgrad else None, step, lr, beta1, beta2, eps, wd, amsgrad)
-                            done = True
-                if not done:
-                    general += store.params
+                if store.attached() and store.grads_attached():
+                    if not store.grad_written:           # zero_grad(set_to_none=True) and nothing since: "grad is None"
+                        continue
+                    fs = self._flat_state(store, amsgrad)
+                    pst = fs["pstates"]
+                    if pst[0]["step"] == pst[len(pst) // 2]["step"] == pst[-1]["step"]:
+                        self._step_flat(store, fs, lr, beta1, beta2, eps, wd, amsgrad)
+                        continue
+                general += store.params
             if not general:
                 continue
             todo = [p for p in general if p.grad is not None]
@@ -212,7 +212,7 @@ class Adam(Optimizer):
                 raise RuntimeError("Adam does not support sparse gradients, please consider SparseAdam instead")
             in_group = set(id(p) for p in todo)
             # ---- parameters that live in a flat store, one sequence of ops per store
-            stores, seen = [], set()
+            flat_ids, seen = set(), set()
             for p in todo:
                 store = getattr(p, "_dpf_flat", None)
                 if store is None or id(store) in seen:
@@ -220,19 +220,11 @@ class Adam(Optimizer):
                 seen.add(id(store))
                 steps = set(self.state[q].get("step", 0) if q in self.state else 0 for q in store.params)
                 if store.attached() and all(id(q) in in_group for q in store.params) and len(steps) == 1 and \
-                        all(q.grad is g for q, g in zip(store.params, store.gviews)):
-                    stores.append(store)
-            flat_ids = set()
-            for store in stores:
-                fs = self._flat_state(store, amsgrad)
-                step = self.state[store.params[0]]["step"] + 1
-                for q in store.params:
-                    self.state[q]["step"] = step
-                    flat_ids.add(id(q))
-                if not self._update_flat(store.flat_p, store.flat_g, fs["buf"]["exp_avg"], fs["buf"]["exp_avg_sq"],
-                                         fs["buf"]["max_exp_avg_sq"] if amsgrad else None, step, lr, beta1, beta2, eps, wd, amsgrad):
-                    self._update([store.flat_p], [store.flat_g], [fs["buf"]["exp_avg"]], [fs["buf"]["exp_avg_sq"]],
-                                 [fs["buf"]["max_exp_avg_sq"]] if amsgrad else None, step, lr, beta1, beta2, eps, wd, amsgrad)
+                        store.grads_attached(full=True):
+                    fs = self._flat_state(store, amsgrad)
+                    fs["pstates"] = [self.state[q] for q in store.params]      # (this path trusts no cached list)
+                    self._step_flat(store, fs, lr, beta1, beta2, eps, wd, amsgrad)
+                    flat_ids.update(map(id, store.params))
             # ---- everything else, multi-tensor, grouped by step count (and device / dtype)
             buckets = {}
             for p in todo:

@@ -18,14 +18,11 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .layers import Swish
-from .flowlist import FlowList
+from .layers import Swish, PackedWeights, weight_state, _needs_autograd
+from .flat_store import ParamStore
+from .flowlist import FlowList, tag_layer_sum
+from .train_engine import update_running_stats
 from .._lib import lib, check, current_stream, MODE
-
-
-def _needs_autograd(*tensors):
-    from .flows import _needs_autograd as point_flow_rule          # (one rule, one warning class: flows.EvalModeAutogradWarning)
-    return point_flow_rule(*tensors)
 
 
 def pattern_code(warp_inds, G):
@@ -40,31 +37,7 @@ def pattern_code(warp_inds, G):
     return None
 
 
-class _PackedWeights:
-    """Mixin: the packed eval-mode weights are rebuilt after anything that may have changed the parameters behind the
-    version counters' back -- optimizers update through `.data` -- i.e. on every train()/eval() switch, load_state_dict,
-    .to()/.cuda()/.float(); in between, the stack's sentinels catch ordinary in-place edits."""
-
-    def invalidate_packed(self):
-        st = self.__dict__.get("_stack")
-        if st is not None:
-            st.invalidate()
-
-    def train(self, mode=True):
-        if mode != self.training:
-            self.invalidate_packed()
-        return super().train(mode)
-
-    def _apply(self, fn, *a, **kw):
-        self.invalidate_packed()
-        return super()._apply(fn, *a, **kw)
-
-    def _load_from_state_dict(self, *a, **kw):
-        self.invalidate_packed()
-        return super()._load_from_state_dict(*a, **kw)
-
-
-class RealNVPFlow(_PackedWeights, nn.Module):
+class RealNVPFlow(PackedWeights, nn.Module):
     def __init__(self, n_features, g_n_features, weight_std=0.01, warp_inds=[0], eps=1e-6):
         super().__init__()
         self.n_features = n_features
@@ -84,7 +57,6 @@ class RealNVPFlow(_PackedWeights, nn.Module):
                 net[-1].weight.normal_(std=weight_std)
                 net[-1].bias.zero_()
             setattr(self, "T_%s_0" % br, net)
-        self._stack = None
 
     def canon_pieces(self):
         """The step's tensors in dpf_gprior_pack's canonical order (include/dpf_hip.h)."""
@@ -112,14 +84,12 @@ class RealNVPFlow(_PackedWeights, nn.Module):
         if mode not in ("direct", "inverse"):
             raise ValueError(mode)
         if _fusable(self, [self], g):
-            if self._stack is None:
-                self.__dict__["_stack"] = GPriorStack([self])
-            _, _, gs, mus, lvs = self._stack.run(g, mode)
+            _, _, gs, mus, lvs = self.packed_stack(lambda: GPriorStack([self])).run(g, mode)
             return gs[0], mus[0], lvs[0]
         return self.forward_torch(g, mode)
 
 
-class RealNVPFlowCouple(_PackedWeights, nn.Module):
+class RealNVPFlowCouple(PackedWeights, nn.Module):
     def __init__(self, n_features, g_n_features, weight_std=0.01, pattern=0):
         super().__init__()
         self.n_features = n_features
@@ -154,14 +124,12 @@ class RealNVPFlowCouple(_PackedWeights, nn.Module):
         if mode not in ("direct", "inverse"):
             raise ValueError(mode)
         if _fusable(self, self.layers(), g):
-            if self.__dict__.get("_stack") is None:
-                self.__dict__["_stack"] = GPriorStack(self.layers())
-            _, _, gs, mus, lvs = self._stack.run(g, mode)
+            _, _, gs, mus, lvs = self.packed_stack(lambda: GPriorStack(self.layers())).run(g, mode)
             return list(gs.unbind(0)), list(mus.unbind(0)), list(lvs.unbind(0))
         return self.forward_torch(g, mode)
 
 
-class GlobalRNVPDecoder(_PackedWeights, nn.Module):
+class GlobalRNVPDecoder(PackedWeights, nn.Module):
     def __init__(self, n_flows, n_features, g_n_features, weight_std=0.01):
         super().__init__()
         self.n_flows = n_flows
@@ -179,13 +147,10 @@ class GlobalRNVPDecoder(_PackedWeights, nn.Module):
         return out
 
     def stack(self):
-        if self.__dict__.get("_stack") is None:
-            self.__dict__["_stack"] = GPriorStack(self.coupling_layers())
-        return self._stack
+        return self.packed_stack(lambda: GPriorStack(self.coupling_layers()))
 
     def flatten_parameters(self):
         """Opt in to the flat parameter store (see PriorFlatStore); returns it.  Call after .cuda()."""
-        _adopt_flatstore_methods()
         steps = self.coupling_layers()
         dev = next(self.parameters()).device
         store = self.__dict__.get("_flat")
@@ -283,14 +248,12 @@ def _train_backward(g, canon, params_only, gs, mus, lvs, save_h, stats, dlists, 
     return dg, dcanon
 
 
-class PriorFlatStore:
-    """All parameters of a GlobalRNVPDecoder in ONE buffer laid out exactly as the training kernels read them (the
-    parameters-only canonical block of include/dpf_hip.h) and their gradients in its twin -- the counterpart of
-    train_engine.FlatStore for the latent prior flow.  Every nn.Parameter keeps its identity, name and shape; its `.data`
-    becomes a view of `flat_p`, its `.grad` a view of `flat_g`.  The forward then needs no gather, the backward adds its
-    gradient block with one op instead of feeding 10 tensors per step to AccumulateGrad nodes, networks.optimizers.Adam
-    updates the whole store with one op sequence, and the data-parallel exchange is one all-reduce
-    (distributed.allreduce_flat_gradients).  As with FlatStore, per-parameter autograd hooks do not fire."""
+class PriorFlatStore(ParamStore):
+    """The ParamStore of a GlobalRNVPDecoder, laid out exactly as the training kernels read the parameters (the
+    parameters-only canonical block of include/dpf_hip.h) -- the counterpart of train_engine.FlatStore for the latent prior
+    flow.  The forward then needs no gather, the backward adds its gradient block with one op instead of feeding 10 tensors
+    per step to AccumulateGrad nodes, networks.optimizers.Adam updates the whole store with one op sequence, and the
+    data-parallel exchange is one all-reduce (distributed.allreduce_flat_gradients)."""
 
     def __init__(self, layers, dev):
         params, slots, off = [], [], 0
@@ -299,48 +262,12 @@ class PriorFlatStore:
                 net = getattr(l, "T_%s_0" % br)
                 for t in (net[0].weight, net[1].weight, net[1].bias, net[3].weight, net[3].bias):
                     params.append(t); slots.append((off, t.numel())); off += t.numel()
-        self.params, self.total, self._slots = params, off, slots
-        self.flat_p = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.flat_g = torch.zeros_like(self.flat_p)
-        with torch.no_grad():
-            torch._foreach_copy_([self.flat_p[o:o + n] for o, n in slots], [t.detach().reshape(-1).to(dev) for t in params])
-        self.pviews = [self.flat_p[o:o + n].view(t.shape) for (o, n), t in zip(slots, params)]
-        self.gviews = [self.flat_g[o:o + n].view(t.shape) for (o, n), t in zip(slots, params)]
-        self.grad_written = any(t.grad is not None for t in params)     # see FlatStore.grad_written
-        for t, pv, gv in zip(params, self.pviews, self.gviews):
-            if t.grad is not None:
-                gv.copy_(t.grad)
-            t.data = pv
-            t.grad = gv
-            t._dpf_flat = self
-        from .train_engine import hook_grad_written
-        hook_grad_written(params)
-        self.token = torch.zeros(1, dtype=torch.float32, device=dev, requires_grad=True)
-
-    def attached(self):
-        a, b = self.params[0], self.params[-1]
-        return a.data_ptr() == self.pviews[0].data_ptr() and b.data_ptr() == self.pviews[-1].data_ptr() and a.device == self.flat_p.device
-
-    def rebase_grads(self, buf):
-        """As FlatStore.rebase_grads: the gradient buffer becomes `buf` (a slice of distributed.GradArena's message)."""
-        assert buf.numel() == self.flat_g.numel() and buf.dtype == torch.float32 and buf.is_contiguous() and buf.device == self.flat_g.device
-        with torch.no_grad():
-            buf.copy_(self.flat_g)
-        self.flat_g = buf
-        self.gviews = [buf[o:o + n].view(t.shape) for (o, n), t in zip(self._slots, self.params)]
-        for t, gv in zip(self.params, self.gviews):
-            t.grad = gv
+        super().__init__(params, slots, off, dev)
 
     def accumulate(self, dcanon):
         self.attach_grads()
         self.grad_written = True
         self.flat_g.add_(dcanon)
-
-
-def _adopt_flatstore_methods():
-    from .train_engine import FlatStore
-    PriorFlatStore.attach_grads = FlatStore.attach_grads          # same bookkeeping over params / gviews / flat_g
-    PriorFlatStore.zero_grad = FlatStore.zero_grad
 
 
 class _GPriorTrainFlat(torch.autograd.Function):
@@ -372,12 +299,8 @@ class _GPriorTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, g, mode, codes, dims, bn_eps, eps, slots, total, *params):
-        S, G, nf = dims
-        B = g.shape[0]
-        L_ = lib()
         g = g.contiguous()
-        dev = g.device
-        canon = torch.zeros(total, dtype=torch.float32, device=dev)
+        canon = torch.zeros(total, dtype=torch.float32, device=g.device)
         torch._foreach_copy_([canon[o:o + n] for o, n in slots], [p.detach().reshape(-1) for p in params])
         gs, mus, lvs, save_h, stats = _train_forward(g, canon, 0, mode, codes, dims, bn_eps, eps)
         ctx.save_for_backward(g, canon, gs, mus, lvs, save_h, stats, *params)
@@ -390,11 +313,8 @@ class _GPriorTrain(torch.autograd.Function):
     def backward(ctx, d_gs, d_mus, d_lvs, _):
         g, canon, gs, mus, lvs, save_h, stats = ctx.saved_tensors[:7]
         params = ctx.saved_tensors[7:]
-        mode, codes, (S, G, nf), bn_eps, eps, slots = ctx.cfg
-        B = g.shape[0]
-        L_ = lib()
-        dev = g.device
-        dg, dcanon = _train_backward(g, canon, 0, gs, mus, lvs, save_h, stats, (d_gs, d_mus, d_lvs), mode, codes, (S, G, nf), bn_eps, eps)
+        mode, codes, dims, bn_eps, eps, slots = ctx.cfg
+        dg, dcanon = _train_backward(g, canon, 0, gs, mus, lvs, save_h, stats, (d_gs, d_mus, d_lvs), mode, codes, dims, bn_eps, eps)
         grads = [torch.empty_like(p) for p in params]
         torch._foreach_copy_(grads, [dcanon[o:o + n].view_as(p) for (o, n), p in zip(slots, params)])
         return (dg if ctx.needs_input_grad[0] else None, None, None, None, None, None, None, None, *grads)
@@ -423,27 +343,15 @@ def run_training_prior(module, layers, g, mode):
             gs, mus, lvs, stats = _GPriorTrainFlat.apply(g, store.token, store, mode, codes, dims, bns[0].eps, eps)
         else:
             gs, mus, lvs, stats = _GPriorTrain.apply(g, mode, codes, dims, bns[0].eps, eps, slots, total, *params)
-        # running statistics (nn.BatchNorm1d: momentum 0.1, unbiased variance), multi-tensor
+        # running statistics (nn.BatchNorm1d: momentum 0.1, unbiased variance)
         B, nf = g.shape[0], dims[2]
         with torch.no_grad():
-            m = bns[0].momentum
-            means = list(stats[:, 0].reshape(-1, nf).unbind(0))
-            uvars = list((stats[:, 1] * (B / (B - 1.0))).reshape(-1, nf).unbind(0))
-            rms, rvs = [b.running_mean for b in bns], [b.running_var for b in bns]
-            torch._foreach_mul_(rms, 1.0 - m)
-            torch._foreach_add_(rms, means, alpha=m)
-            torch._foreach_mul_(rvs, 1.0 - m)
-            torch._foreach_add_(rvs, uvars, alpha=m)
-            torch._foreach_add_([b.num_batches_tracked for b in bns], 1)
-    lv_list = list(lvs.unbind(0))
+            update_running_stats(bns, list(stats[:, 0].reshape(-1, nf).unbind(0)),
+                                 list((stats[:, 1] * (B / (B - 1.0))).reshape(-1, nf).unbind(0)))
     # the layer-sum of the log-variances, which is all GaussianFlowNLL wants of them (losses.py:22): one reduction over the
     # (S,B,G) block and one expand in the backward instead of S - 1 adds and S gradient slices stacked back; tagged like the
     # point decoder's list (networks.losses.total_logvar recognises the whole list)
-    token = object()
-    for i, v in enumerate(lv_list):
-        v._dpf_pos = (token, i)
-    lv_list[-1]._dpf_total = (token, len(lv_list), lvs.sum(0))
-    return list(gs.unbind(0)), list(mus.unbind(0)), lv_list
+    return list(gs.unbind(0)), list(mus.unbind(0)), tag_layer_sum(list(lvs.unbind(0)), lvs.sum(0))
 
 
 class GPriorStack:
@@ -464,7 +372,7 @@ class GPriorStack:
         self._packed = None
 
     def _ensure(self, device):
-        state = tuple((t._version, t.data_ptr()) for t in self._sentinels)
+        state = weight_state(self._sentinels)
         if state != self._state or self._packed is None or self._packed.device != device:
             L_ = lib()
             S = len(self.layers)
@@ -482,7 +390,6 @@ class GPriorStack:
 
     def run(self, g, mode, want_lists=True):
         """g (B,G) fp32 CUDA -> (g_out (B,G), sum_logvar (B,G), gs, mus, lvs (S,B,G) in DIRECT order or None)."""
-        import ctypes
         if not g.is_cuda:
             raise RuntimeError("the fused prior flow runs on MI355X only (g must be a CUDA tensor); there is no CPU fallback")
         if g.dtype != torch.float32 or g.dim() != 2 or g.shape[1] != self.G:

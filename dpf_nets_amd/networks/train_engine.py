@@ -26,6 +26,8 @@ import torch
 
 from .._lib import lib, check, current_stream, PREC, MODE
 from .engine import layer_meta
+from .flat_store import ParamStore, hook_grad_written            # noqa: F401  (hook_grad_written: re-exported)
+from .flowlist import tag_layer_sum
 
 F = 64
 # precision of the forward contraction and of its recomputation in the backward passes (which fixes
@@ -188,8 +190,8 @@ class StackSpec:
         return out
 
 
-def _update_running(bns, means, uvars):
-    """running = (1 - momentum) * running + momentum * batch  (nn.BatchNorm1d, momentum 0.1)"""
+def update_running_stats(bns, means, uvars):
+    """running = (1 - momentum) * running + momentum * batch  (nn.BatchNorm1d, momentum 0.1), multi-tensor"""
     m = bns[0].momentum
     rms, rvs, nbt = [b.running_mean for b in bns], [b.running_var for b in bns], [b.num_batches_tracked for b in bns]
     torch._foreach_mul_(rms, 1.0 - m)
@@ -265,8 +267,8 @@ def _forward_core(p, g, spec, mode, prec, tcanon, W0, gam, bet, W1, b1, flat=Non
     elif flat is not None:
         flat.update_running(film_mean, film_uvar, flow_mean, flow_uvar, mods[0][1].momentum)
     else:
-        _update_running([m[1] for m in mods], list(film_mean.unbind(0)), list(film_uvar.unbind(0)))
-        _update_running(spec.flow_bns(), list(flow_mean.unbind(0)), list(flow_uvar.unbind(0)))
+        update_running_stats([m[1] for m in mods], list(film_mean.unbind(0)), list(film_uvar.unbind(0)))
+        update_running_stats(spec.flow_bns(), list(flow_mean.unbind(0)), list(flow_uvar.unbind(0)))
     # 3L output tensors (autograd hands back one gradient each) + the layer-sum of the log-variances, which is what
     # PointFlowNLL wants of them (losses.py:13): one reduction here instead of L-1 adds and L-1 backward nodes there
     outs = ps.unbind(0) + mus.unbind(0) + lvs.unbind(0) + (lvs.sum(0),)
@@ -404,77 +406,32 @@ class _FlowStackTrain(torch.autograd.Function):
         return (chain if ctx.needs_input_grad[0] else None, dg, None, None, None, *grads)
 
 
-def _mark_grad_written(p):
-    st = getattr(p, "_dpf_flat", None)
-    if st is not None:
-        st.grad_written = True
-
-
-def hook_grad_written(params):
-    """`grad_written` is a HINT that the store's own writers keep up to date (accumulate, attach_grads, the exchanges);
-    gradients that reach flat_g by ordinary autograd -- AccumulateGrad adding in place into the attached views: the
-    tensor-op path of a flattened decoder (DPF_TRAIN_IMPL=torch, forward_torch), an eval-mode decoder under autograd,
-    forward(n_layers=...), a single flow module's own forward -- set it through a post-accumulate hook on every parameter
-    (registered once per Parameter object; the store is looked up at call time, so a rebuilt store is found).  The hooks
-    never fire on the flat path, whose node writes flat_g itself."""
-    for t in params:
-        if not getattr(t, "_dpf_gw_hook", False):
-            t.register_post_accumulate_grad_hook(_mark_grad_written)
-            t._dpf_gw_hook = True
-
-
-class FlatStore:
-    """ONE fp32 buffer that owns the storage of every parameter of the stack, laid out as the kernels and the batched
-    FiLM ops consume it -- [conditioner block (L, 2*T_BR) | W0 (K,F,G) | gamma (K,F) | beta (K,F) | W1 (K,F,F) | b1 (K,F)] --
-    a twin buffer for the gradients, and (8L, F) blocks for the BatchNorm running statistics.  Every nn.Parameter /
-    buffer of the layers keeps its identity, name and shape (state dicts and optimizers are unaffected); its `.data`
-    becomes a view of the flat buffer and its `.grad` a view of the gradient buffer.
+class FlatStore(ParamStore):
+    """The ParamStore of the point decoder's stack, laid out as the kernels and the batched FiLM ops consume it --
+    [conditioner block (L, 2*T_BR) | W0 (K,F,G) | gamma (K,F) | beta (K,F) | W1 (K,F,F) | b1 (K,F)] -- plus (8L, F)
+    blocks for the BatchNorm running statistics (the buffers of the layers become views of them).
 
     What it buys (n_flows=21: 2016 parameters, 504 BatchNorm buffers): the forward needs no gather, the backward adds
     its result blocks into the gradient buffer with six tensor ops instead of handing 2016 tensors to 2016
-    AccumulateGrad nodes, and the data-parallel gradient exchange is one all-reduce of `flat_g`.
-
-    Gradients are written by the node itself (autograd sees only p, g and a token), so per-parameter autograd hooks
-    (and with them DistributedDataParallel's reducer) do not fire for these parameters: use
-    dpf_nets_amd.distributed.allreduce_flat_gradients.  `optimizer.zero_grad()` may set the grads to None; the next
-    backward re-attaches the views (zeroed) -- `FlatStore.zero_grad()` avoids that per-parameter pass."""
+    AccumulateGrad nodes, and the data-parallel gradient exchange is one all-reduce of `flat_g`."""
 
     def __init__(self, spec, dev):
         L, G = spec.L, spec.G
         K = 4 * L
-        cp, fp = spec.canon_params(), spec.film_params()
         sizes = [L * 2 * _T_BR, K * F * G, K * F, K * F, K * F * F, K * F]
-        shapes = [(L, 2 * _T_BR), (K, F, G), (K, 1, F), (K, 1, F), (K, F, F), (K, 1, F)]
-        self.flat_p = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)
-        self.flat_g = torch.zeros_like(self.flat_p)
         offs = [0]
         for n in sizes:
             offs.append(offs[-1] + n)
-        self._offs, self._shapes = offs, shapes
-        self.blocks = [self.flat_p[offs[i]:offs[i + 1]].view(shapes[i]) for i in range(6)]
-        self.gblocks = [self.flat_g[offs[i]:offs[i + 1]].view(shapes[i]) for i in range(6)]
+        self._offs, self._shapes = offs, [(L, 2 * _T_BR), (K, F, G), (K, 1, F), (K, 1, F), (K, F, F), (K, 1, F)]
         # element range of every parameter inside the flat buffers, in spec.all_params() order
-        ranges = [(o, n) for o, n in spec.canon_slots]
+        slots = list(spec.canon_slots)
         for k in range(K):
-            ranges += [(offs[1] + k * F * G, F * G), (offs[2] + k * F, F), (offs[3] + k * F, F),
-                       (offs[4] + k * F * F, F * F), (offs[5] + k * F, F)]
-        self._ranges = ranges
-        self.params = cp + fp
-        had_grad = any(t.grad is not None for t in self.params)
-        with torch.no_grad():
-            torch._foreach_copy_([self.flat_p[o:o + n] for o, n in ranges], [t.detach().reshape(-1).to(dev) for t in self.params])
-        self.pviews = [self.flat_p[o:o + n].view(t.shape) for (o, n), t in zip(ranges, self.params)]
-        self.gviews = [self.flat_g[o:o + n].view(t.shape) for (o, n), t in zip(ranges, self.params)]
-        for t, pv, gv in zip(self.params, self.pviews, self.gviews):
-            if t.grad is not None:
-                gv.copy_(t.grad)
-            t.data = pv
-            t.grad = gv
-            t._dpf_flat = self              # networks.optimizers.Adam updates a whole store at once
-        hook_grad_written(self.params)
+            slots += [(offs[1] + k * F * G, F * G), (offs[2] + k * F, F), (offs[3] + k * F, F),
+                      (offs[4] + k * F * F, F * F), (offs[5] + k * F, F)]
+        super().__init__(spec.canon_params() + spec.film_params(), slots, offs[-1], dev)
+        self.blocks, self.gblocks = self._blocks_of(self.flat_p), self._blocks_of(self.flat_g)
         # BatchNorm running statistics: [FiLM nets (4L) | conditioner stacks (4L)]
         self.bns = [m[1] for m in spec.film_modules()] + spec.flow_bns()
-        nb = len(self.bns)
         self.rm = torch.stack([b.running_mean.detach().to(dev) for b in self.bns])
         self.rv = torch.stack([b.running_var.detach().to(dev) for b in self.bns])
         self.nbt = torch.stack([b.num_batches_tracked.detach().to(dev) for b in self.bns])
@@ -482,32 +439,17 @@ class FlatStore:
             b.running_mean.data = self.rm[i]
             b.running_var.data = self.rv[i]
             b.num_batches_tracked.data = self.nbt[i]
-        self.nfilm = nb // 2
-        self.token = torch.zeros(1, dtype=torch.float32, device=dev, requires_grad=True)
-        # a gradient was written into flat_g since the last zero_grad(set_to_none=True) -- what "p.grad is not None" means
-        # for parameters whose .grad views stay attached (networks.optimizers.Adam skips a store without one)
-        self.grad_written = had_grad
+        self.nfilm = len(self.bns) // 2
+
+    def _blocks_of(self, buf):
+        return [buf[self._offs[i]:self._offs[i + 1]].view(self._shapes[i]) for i in range(6)]
 
     def attached(self):
-        """The aliasing survives in-place updates, load_state_dict and optimizer steps; module.to()/.cuda()/.float()
-        re-assign `.data` and break it (the decoder then builds a new store)."""
-        a, b, pv, bn = self.params[0], self.params[-1], self.pviews, self.bns[-1]
-        return (a.data_ptr() == pv[0].data_ptr() and b.data_ptr() == pv[-1].data_ptr() and
-                bn.running_var.data_ptr() == self.rv[-1].data_ptr() and a.device == self.flat_p.device)
+        return super().attached() and self.bns[-1].running_var.data_ptr() == self.rv[-1].data_ptr()
 
     def rebase_grads(self, buf):
-        """Move the gradient buffer onto `buf` (a contiguous fp32 slice of a bigger buffer, same length): contents carried
-        over, every parameter's .grad re-pointed.  distributed.GradArena uses this to make the gradients of a whole model
-        -- this store, the prior flow's store, every other parameter -- ONE flat message."""
-        assert buf.numel() == self.flat_g.numel() and buf.dtype == torch.float32 and buf.is_contiguous() and buf.device == self.flat_g.device
-        with torch.no_grad():
-            buf.copy_(self.flat_g)
-        self.flat_g = buf
-        offs, shapes = self._offs, self._shapes
-        self.gblocks = [buf[offs[i]:offs[i + 1]].view(shapes[i]) for i in range(6)]
-        self.gviews = [buf[o:o + n].view(t.shape) for (o, n), t in zip(self._ranges, self.params)]
-        for t, gv in zip(self.params, self.gviews):
-            t.grad = gv
+        super().rebase_grads(buf)
+        self.gblocks = self._blocks_of(buf)
 
     def update_running_fused(self, L, film_mean, film_uvar, stats, momentum):
         """All 8 L running-statistics updates in one launch (r03: ~9 tensor-op launches before); same arithmetic, same bits."""
@@ -524,32 +466,6 @@ class FlatStore:
         self.rv[:n].add_(film_uvar, alpha=momentum)
         self.rv[n:].add_(flow_uvar, alpha=momentum)
         self.nbt.add_(1)
-
-    def zero_grad(self):
-        self.flat_g.zero_()
-        self.grad_written = False
-        self.attach_grads(zeroed=True)
-
-    def attach_grads(self, zeroed=False, full=False):
-        """Make every parameter's .grad the view of flat_g again: after optimizer.zero_grad(set_to_none=True) the views
-        come back zeroed; a .grad that was replaced by another tensor is copied in.  The per-step check looks at
-        three sentinel parameters only (first, middle, last); full=True examines all of them."""
-        ps, gv = self.params, self.gviews
-        if not full and ps[0].grad is gv[0] and ps[-1].grad is gv[-1] and ps[len(ps) // 2].grad is gv[len(ps) // 2]:
-            return
-        if not zeroed:
-            if all(t.grad is None for t in ps):
-                self.flat_g.zero_()
-                self.grad_written = False
-            else:
-                self.grad_written = True
-                for t, v in zip(ps, gv):
-                    if t.grad is None:
-                        v.zero_()
-                    elif t.grad is not v:
-                        v.copy_(t.grad)
-        for t, v in zip(ps, gv):
-            t.grad = v
 
     def film_grad_blocks(self):
         """The five FiLM-net gradient blocks of flat_g for the fused backward kernel to ADD into (views attached first)."""
@@ -623,9 +539,5 @@ def run_training_stack(spec, p, g, mode, precision=None):
                 precision = spec.f16_range_monitor(None, p.shape[0] * p.shape[2])
             outs = _FlowStackTrain.apply(p, g, spec, mode, PREC[precision], *spec.all_params())
     L = spec.L
-    lvs = list(outs[2 * L:3 * L])
-    token = object()                       # losses.total_logvar recognises the whole list and takes the layer-sum
-    for i, v in enumerate(lvs):
-        v._dpf_pos = (token, i)
-    lvs[-1]._dpf_total = (token, L, outs[3 * L])
-    return list(outs[:L]), list(outs[L:2 * L]), lvs
+    # losses.total_logvar recognises the whole list and takes the layer-sum
+    return list(outs[:L]), list(outs[L:2 * L]), tag_layer_sum(list(outs[2 * L:3 * L]), outs[3 * L])

@@ -514,3 +514,112 @@ def test_compiled_structural_losses_extension_builds_and_exports_the_reference_n
         assert callable(getattr(native, name)), name
     with pytest.raises(RuntimeError, match="must be a CUDA tensor"):
         native.NNDistance(torch.zeros(1, 4, 3), torch.zeros(1, 4, 3))
+
+
+def test_prior_flat_store_built_directly_has_its_own_zero_grad_and_attach_grads():
+    """A PriorFlatStore built from the coupling layers alone (GlobalRNVPDecoder.flatten_parameters() is never called here) is
+    a whole store: zero_grad() and attach_grads(full=True) are its own methods, and each leaves every .grad a zeroed view of
+    flat_g with grad_written False.  CPU tensors, no kernels."""
+    from dpf_nets_amd import networks as nets
+    from dpf_nets_amd.networks.prior_flows import PriorFlatStore
+    torch.manual_seed(11)
+    prior = nets.GlobalRNVPDecoder(2, 8, 6)
+    store = PriorFlatStore(prior.coupling_layers(), torch.device("cpu"))
+    lo, hi = store.flat_g.data_ptr(), store.flat_g.data_ptr() + 4 * store.flat_g.numel()
+
+    def zeroed_views():
+        return all(p.grad is v and lo <= p.grad.data_ptr() < hi and p.grad.shape == p.shape for p, v in zip(store.params, store.gviews)) \
+            and float(store.flat_g.abs().sum()) == 0.0 and not store.grad_written
+    assert store.attached() and list(prior.parameters()) and all(p._dpf_flat is store for p in prior.parameters())
+    store.flat_g.normal_(); store.grad_written = True                    # stale content, as a backward leaves it
+    store.zero_grad()
+    assert zeroed_views()
+    store.flat_g.normal_(); store.grad_written = True
+    for p in store.params:                                               # optimizer.zero_grad(set_to_none=True)
+        p.grad = None
+    store.attach_grads(full=True)
+    assert zeroed_views()
+    store.zero_grad()
+    assert zeroed_views()
+
+
+def test_both_flat_stores_share_one_base_and_rebase_their_gradients():
+    """train_engine.FlatStore and prior_flows.PriorFlatStore are the one flat_store.ParamStore; rebase_grads(buf) onto a slice
+    of a larger buffer (distributed.GradArena's message) carries the gradient values over and makes every p.grad a view of
+    `buf`; FlatStore rebuilds its gradient blocks, so accumulate() lands in `buf`.  CPU tensors, no kernels."""
+    from dpf_nets_amd import networks as nets
+    from dpf_nets_amd.networks.flat_store import ParamStore
+    from dpf_nets_amd.networks.flows import stack_spec
+    from dpf_nets_amd.networks.prior_flows import PriorFlatStore
+    from dpf_nets_amd.networks.train_engine import FlatStore
+    torch.manual_seed(12)
+    cpu = torch.device("cpu")
+    dec = nets.LocalCondRNVPDecoder(1, 64, 8)
+    fs = stack_spec(dec, dec.coupling_layers()).flatten(cpu)
+    ps = PriorFlatStore(nets.GlobalRNVPDecoder(2, 8, 6).coupling_layers(), cpu)
+    assert type(fs) is FlatStore and isinstance(fs, ParamStore) and isinstance(ps, ParamStore)
+    assert FlatStore.attach_grads is ParamStore.attach_grads and PriorFlatStore.attach_grads is ParamStore.attach_grads
+    assert FlatStore.zero_grad is ParamStore.zero_grad and PriorFlatStore.zero_grad is ParamStore.zero_grad
+    for store in (fs, ps):
+        n = store.flat_g.numel()
+        store.flat_g.normal_()
+        old = store.flat_g.clone()
+        big = torch.full((n + 128,), 9.0)
+        buf = big[64:64 + n]
+        store.rebase_grads(buf)
+        assert store.flat_g is buf and torch.equal(buf, old) and bool((big[:64] == 9).all()) and bool((big[64 + n:] == 9).all())
+        lo = buf.data_ptr()
+        for p, (o, k) in zip(store.params, store.slots):
+            assert p.grad.data_ptr() == lo + 4 * o and p.grad.shape == p.shape and torch.equal(p.grad.reshape(-1), old[o:o + k])
+        assert store.grads_attached(full=True) and store.attached()
+    # FlatStore: known blocks accumulate into the new buffer
+    old = fs.flat_g.clone()
+    blocks = [torch.randn_like(b) for b in fs.gblocks]
+    fs.accumulate(blocks[0], blocks[1], blocks[2].squeeze(1), blocks[3].squeeze(1), blocks[4], blocks[5].squeeze(1))
+    assert torch.equal(fs.flat_g, old + torch.cat([b.reshape(-1) for b in blocks])) and fs.grad_written
+    # PriorFlatStore: its one block does too
+    old, d = ps.flat_g.clone(), torch.randn(ps.total)
+    ps.accumulate(d)
+    assert torch.equal(ps.flat_g, old + d) and ps.grad_written
+
+
+class _CountingStack:
+    def __init__(self):
+        self.calls = 0
+
+    def invalidate(self):
+        self.calls += 1
+
+
+def test_every_flow_module_drops_its_packed_weights_on_load_apply_and_mode_switch():
+    """The one PackedWeights mixin serves the five module classes that cache a fused eval-mode stack: load_state_dict, _apply
+    (.to() / .cuda() / .float()) and a train() / eval() SWITCH each invalidate it (a train() call that changes nothing does
+    not).  Checked with a stub where the mixin keeps `_stack`: the instance __dict__, outside nn.Module's registries."""
+    from dpf_nets_amd import networks as nets
+    from dpf_nets_amd.networks.flows import CondRealNVPFlow3D
+    from dpf_nets_amd.networks.layers import PackedWeights
+    from dpf_nets_amd.networks.prior_flows import RealNVPFlow, RealNVPFlowCouple
+    mods = [CondRealNVPFlow3D(64, 8, warp_inds=[1]), nets.LocalCondRNVPDecoder(1, 64, 8), RealNVPFlow(8, 6, warp_inds=[0, 2, 4]),
+            RealNVPFlowCouple(8, 6, pattern=1), nets.GlobalRNVPDecoder(2, 8, 6)]
+    for m in mods:
+        name = type(m).__name__
+        assert isinstance(m, PackedWeights) and m._stack is None, name
+        keys = list(m.state_dict())
+        stub = m.__dict__["_stack"] = _CountingStack()
+        assert m._stack is stub and "_stack" not in m._modules and "_stack" not in m._buffers and "_stack" not in m._parameters, name
+        assert list(m.state_dict()) == keys, name
+        m.load_state_dict(m.state_dict())
+        assert stub.calls == 1, name
+        m._apply(lambda t: t)
+        assert stub.calls == 2, name
+        m.float()
+        assert stub.calls == 3, name
+        assert m.training
+        m.train()                                                        # no switch: the packed weights stay
+        assert stub.calls == 3, name
+        m.eval()
+        assert stub.calls == 4, name
+        m.eval()
+        assert stub.calls == 4, name
+        m.train()
+        assert stub.calls == 5, name
