@@ -63,6 +63,12 @@ SIGNATURES = {
                                      _vp, _f, _vp, _vp]),
     "dpf_flow_train_backward_lists": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                            _vp, _f, _vp, _vp]),
+    "dpf_flow_frozen_stats_floats": (_sz, []),
+    "dpf_flow_frozen_workspace_bytes": (_sz, [_i, _i]),
+    "dpf_flow_frozen_backward_lists": (_i, [_i] * 5 + [_vp] * 17 + [_f, _vp, _vp]),
+    "dpf_film_frozen_forward": (_i, [_i, _i, _i] + [_vp] * 8 + [_f] + [_vp] * 3 + [_vp]),
+    "dpf_film_frozen_workspace_floats": (_sz, [_i, _i, _i]),
+    "dpf_film_frozen_backward": (_i, [_i, _i, _i] + [_vp] * 16 + [_i, _vp]),
     "dpf_fscore_reduce": (_i, [_i, _i, _i, _vp, _vp, _f, _vp, _vp]),
     "dpf_chamfer_reduce": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     "dpf_encoder_canon_floats": (_sz, []),

@@ -36,6 +36,7 @@ struct FwdArgs {
     float *fm;                   // (K, B, F)
     float *xhat;                 // (K, B, F)
     float *rstd, *mean, *uvar;   // (K, F): 1/sqrt(var + eps), batch mean, unbiased batch variance (running_var update)
+    const float *rmean, *rvar;   // FROZEN: (K, F) running statistics, normalised with instead of the batch's (mean / uvar unused)
 };
 
 __device__ __forceinline__ float sigmoidf_(float y) { return 1.0f / (1.0f + expf(-y)); }
@@ -60,7 +61,8 @@ __device__ __forceinline__ void tile_load(float *lds, const float *src, size_t l
     }
 }
 
-template <int NB>
+// FROZEN (eval mode under autograd, dpf_film_frozen_forward): BatchNorm1d normalises with its running statistics; B >= 1
+template <int NB, bool FROZEN = false>
 __global__ __launch_bounds__(T) void film_train_fwd_kernel(FwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int B = a.B, G = a.G, k = blockIdx.x;
@@ -97,11 +99,18 @@ __global__ __launch_bounds__(T) void film_train_fwd_kernel(FwdArgs a) {
             }
         }
     }
+    float mean, rstd;
+    if constexpr (FROZEN) {
+        mean = a.rmean[(size_t)k * F + f];
+        rstd = 1.0f / sqrtf(a.rvar[(size_t)k * F + f] + a.eps);
+        if (q == 0) a.rstd[(size_t)k * F + f] = rstd;
+        __syncthreads();                                               // every thread is past the W0 tile
+    } else {
     // ---- BatchNorm1d over the batch dimension (two passes, biased variance)
     float s = 0.f;
 #pragma unroll
     for (int bi = 0; bi < NB; ++bi) s += q + 4 * bi < B ? acc[bi] : 0.f;
-    const float mean = group_sum(s, red, f, q) / (float)B;
+    mean = group_sum(s, red, f, q) / (float)B;
     float v = 0.f;
 #pragma unroll
     for (int bi = 0; bi < NB; ++bi) {
@@ -109,11 +118,12 @@ __global__ __launch_bounds__(T) void film_train_fwd_kernel(FwdArgs a) {
         v += q + 4 * bi < B ? d * d : 0.f;
     }
     const float var = group_sum(v, red, f, q) / (float)B;
-    const float rstd = 1.0f / sqrtf(var + a.eps);
+    rstd = 1.0f / sqrtf(var + a.eps);
     if (q == 0) {
         a.rstd[(size_t)k * F + f] = rstd;
         a.mean[(size_t)k * F + f] = mean;
         a.uvar[(size_t)k * F + f] = var * ((float)B / (float)(B - 1));
+    }
     }
     const float gam = a.gam[(size_t)k * F + f], bet = a.bet[(size_t)k * F + f];
     tile_load(ws, a.W1 + (size_t)k * F * F, F, F, W1P, tid);           // (every thread is past the W0 tile: group_sum's barriers)
@@ -158,6 +168,8 @@ struct BwdArgs {
     float *dW1;                  // (K, F, F)
     float *db1;                  // (K, F)
     float *dg_part;              // (K, B, G) or NULL: this sub-net's share of d loss / d g
+    float *dg;                   // FROZEN: (B, G) = the sum of the shares over the K sub-nets, k = 0 .. K - 1 in order
+    unsigned *ticket;            // FROZEN: one word, zero between calls: the workgroup that arrives last sums the shares
 };
 
 __device__ __forceinline__ void put(float *p, float v, int accumulate) { *p = accumulate ? *p + v : v; }
@@ -173,7 +185,9 @@ __device__ __forceinline__ void tile_store(float *dst, size_t ld, const float *l
     }
 }
 
-template <int NB>
+// FROZEN (dpf_film_frozen_backward): the statistics are constants, d u = rstd * gamma * d y (no mean-correction terms), and
+// d g is finished in this launch
+template <int NB, bool FROZEN = false>
 __global__ __launch_bounds__(T) void film_train_bwd_kernel(BwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int B = a.B, G = a.G, k = blockIdx.x;
@@ -260,14 +274,19 @@ __global__ __launch_bounds__(T) void film_train_bwd_kernel(BwdArgs a) {
         }
         const float tg = group_sum(pg, red, f, q);
         const float tb = group_sum(pb, red, f, q);
-        const float m1 = group_sum(p1, red, f, q) / (float)B;
-        const float m2 = group_sum(p2, red, f, q) / (float)B;
         if (q == 0) {
             put(a.dgam + (size_t)k * F + f, tg, a.accumulate);
             put(a.dbet + (size_t)k * F + f, tb, a.accumulate);
         }
+        if constexpr (FROZEN) {
+#pragma unroll
+            for (int bi = 0; bi < NB; ++bi) du[bi] = rstd * du[bi];
+        } else {
+        const float m1 = group_sum(p1, red, f, q) / (float)B;
+        const float m2 = group_sum(p2, red, f, q) / (float)B;
 #pragma unroll
         for (int bi = 0; bi < NB; ++bi) du[bi] = rstd * (du[bi] - m1 - xh[bi] * m2);
+        }
     }
     __syncthreads();                                                   // everyone is done with d fm
 #pragma unroll
@@ -319,9 +338,39 @@ __global__ __launch_bounds__(T) void film_train_bwd_kernel(BwdArgs a) {
                     const f32x4 x = *(const f32x4 *)(d0 + (size_t)bc * F + 4 * i);
                     s = __builtin_fmaf(x.w, wc[4 * i + 3], __builtin_fmaf(x.z, wc[4 * i + 2], __builtin_fmaf(x.y, wc[4 * i + 1], __builtin_fmaf(x.x, wc[4 * i], s))));
                 }
-                if (b < B && j < G) a.dg_part[((size_t)k * B + b) * G + j] = s;
+                if (b < B && j < G) {
+                    // FROZEN: written through (agent scope) -- the last workgroup reads it, possibly from another XCD
+                    if constexpr (FROZEN) __hip_atomic_store(&a.dg_part[((size_t)k * B + b) * G + j], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    else a.dg_part[((size_t)k * B + b) * G + j] = s;
+                }
             }
         }
+    }
+    if constexpr (FROZEN) {
+        // d g = sum over the sub-nets of their shares, by whichever workgroup arrives last, k = 0 .. K - 1 in order: the same
+        // sums in the same order wherever the workgroups ran (the pattern of flow_train.hip's per-cloud totals).  The ticket
+        // returns to zero for the next call.
+        if (a.dg_part == nullptr) return;
+        const int K = gridDim.x;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // this workgroup's share has left the CU
+        __syncthreads();
+        unsigned *tk = (unsigned *)red;
+        if (tid == 0) *tk = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        if (*tk != (unsigned)(K - 1)) return;
+        for (int e = tid; e < B * G; e += T) {
+            float s = 0.f;
+            for (int k0 = 0; k0 < K; k0 += 8) {                        // eight loads in flight, added in order
+                float v[8];
+#pragma unroll
+                for (int i = 0; i < 8; ++i)
+                    v[i] = k0 + i < K ? __hip_atomic_load(&a.dg_part[(size_t)(k0 + i) * B * G + e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) s += v[i];
+            }
+            a.dg[e] = s;
+        }
+        if (tid == 0) __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -341,7 +390,7 @@ extern "C" int dpf_film_train_forward(int K, int B, int G, const float *g, const
                                       float *mean, float *uvar, dpf_stream_t stream) {
     if (K <= 0 || B < 2 || G <= 0 || !g || !W0 || !gamma || !beta || !W1 || !b1 || !fm || !xhat || !rstd || !mean || !uvar) return DPF_EINVAL;
     if (B > 64 || (G & 3)) return DPF_ENOSUP;
-    FwdArgs a = {B, G, bn_eps, g, W0, gamma, beta, W1, b1, fm, xhat, rstd, mean, uvar};
+    FwdArgs a = {B, G, bn_eps, g, W0, gamma, beta, W1, b1, fm, xhat, rstd, mean, uvar, nullptr, nullptr};
     const int lds = (int)fwd_lds(B);
     hipStream_t s = (hipStream_t)stream;
 #define DPF_FWD(NB)                                                                                         \
@@ -363,7 +412,7 @@ extern "C" int dpf_film_train_backward(int K, int B, int G, const float *g, cons
         !dW1 || !db1)
         return DPF_EINVAL;
     if (B > 64 || (G & 3)) return DPF_ENOSUP;
-    BwdArgs a = {B, G, accumulate, g, W0, gamma, beta, W1, xhat, rstd, dfm, dW0, dgamma, dbeta, dW1, db1, dg_part};
+    BwdArgs a = {B, G, accumulate, g, W0, gamma, beta, W1, xhat, rstd, dfm, dW0, dgamma, dbeta, dW1, db1, dg_part, nullptr, nullptr};
     const int lds = (int)bwd_lds(B);
     hipStream_t s = (hipStream_t)stream;
 #define DPF_BWDK(NB)                                                                                        \
@@ -371,6 +420,51 @@ extern "C" int dpf_film_train_backward(int K, int B, int G, const float *g, cons
         static LdsLimit lim;                                                                                \
         if (hipError_t e = lim.ensure((const void *)film_train_bwd_kernel<NB>, lds); e != hipSuccess) return (int)e; \
         hipLaunchKernelGGL(film_train_bwd_kernel<NB>, dim3(K), dim3(T), lds, s, a);                         \
+    }
+    if (B <= 16) DPF_BWDK(4) else if (B <= 32) DPF_BWDK(8) else DPF_BWDK(16)
+#undef DPF_BWDK
+    return (int)hipGetLastError();
+}
+
+// ---- the same nets in eval mode under autograd: frozen running statistics (networks/frozen_engine.py).  B >= 1.
+extern "C" int dpf_film_frozen_forward(int K, int B, int G, const float *g, const float *W0, const float *gamma, const float *beta,
+                                       const float *W1, const float *b1, const float *running_mean, const float *running_var,
+                                       float bn_eps, float *fm, float *xhat, float *rstd, dpf_stream_t stream) {
+    if (K <= 0 || B < 1 || G <= 0 || !g || !W0 || !gamma || !beta || !W1 || !b1 || !running_mean || !running_var || !fm || !xhat || !rstd)
+        return DPF_EINVAL;
+    if (B > 64 || (G & 3)) return DPF_ENOSUP;
+    FwdArgs a = {B, G, bn_eps, g, W0, gamma, beta, W1, b1, fm, xhat, rstd, nullptr, nullptr, running_mean, running_var};
+    const int lds = (int)fwd_lds(B);
+    hipStream_t s = (hipStream_t)stream;
+#define DPF_FWD(NB)                                                                                         \
+    {                                                                                                       \
+        static LdsLimit lim;                                                                                \
+        if (hipError_t e = lim.ensure((const void *)film_train_fwd_kernel<NB, true>, lds); e != hipSuccess) return (int)e; \
+        hipLaunchKernelGGL((film_train_fwd_kernel<NB, true>), dim3(K), dim3(T), lds, s, a);                 \
+    }
+    if (B <= 16) DPF_FWD(4) else if (B <= 32) DPF_FWD(8) else DPF_FWD(16)
+#undef DPF_FWD
+    return (int)hipGetLastError();
+}
+
+extern "C" size_t dpf_film_frozen_workspace_floats(int K, int B, int G) { return K > 0 && B > 0 && G > 0 ? (size_t)K * B * G : 0; }
+
+extern "C" int dpf_film_frozen_backward(int K, int B, int G, const float *g, const float *W0, const float *gamma, const float *beta,
+                                        const float *W1, const float *xhat, const float *rstd, const float *dfm, float *dW0,
+                                        float *dgamma, float *dbeta, float *dW1, float *db1, float *dg, float *workspace,
+                                        unsigned *ticket, int accumulate, dpf_stream_t stream) {
+    if (K <= 0 || B < 1 || G <= 0 || !g || !W0 || !gamma || !beta || !W1 || !xhat || !rstd || !dfm || !dW0 || !dgamma || !dbeta ||
+        !dW1 || !db1 || (dg && (!workspace || !ticket)))
+        return DPF_EINVAL;
+    if (B > 64 || (G & 3)) return DPF_ENOSUP;
+    BwdArgs a = {B, G, accumulate, g, W0, gamma, beta, W1, xhat, rstd, dfm, dW0, dgamma, dbeta, dW1, db1, dg ? workspace : nullptr, dg, ticket};
+    const int lds = (int)bwd_lds(B);
+    hipStream_t s = (hipStream_t)stream;
+#define DPF_BWDK(NB)                                                                                        \
+    {                                                                                                       \
+        static LdsLimit lim;                                                                                \
+        if (hipError_t e = lim.ensure((const void *)film_train_bwd_kernel<NB, true>, lds); e != hipSuccess) return (int)e; \
+        hipLaunchKernelGGL((film_train_bwd_kernel<NB, true>), dim3(K), dim3(T), lds, s, a);                 \
     }
     if (B <= 16) DPF_BWDK(4) else if (B <= 32) DPF_BWDK(8) else DPF_BWDK(16)
 #undef DPF_BWDK

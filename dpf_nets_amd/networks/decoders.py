@@ -9,13 +9,13 @@ tensors runs the HIP training kernels for the whole stack as one autograd node
 (decoders.py:58-70) for CPU tensors / DPF_TRAIN_IMPL=torch."""
 import torch.nn as nn
 
-from .flows import CondRealNVPFlow3DTriple, _needs_autograd, use_hip_training, train_stack, stack_spec
+from .flows import CondRealNVPFlow3DTriple, EvalAutograd, _needs_autograd, use_hip_training, train_stack, stack_spec, frozen_stack
 from .flowlist import FlowList
 from .layers import PackedWeights
 from .engine import FlowStack
 
 
-class LocalCondRNVPDecoder(PackedWeights, nn.Module):
+class LocalCondRNVPDecoder(EvalAutograd, PackedWeights, nn.Module):
     def __init__(self, n_flows, f_n_features, g_n_features, weight_std=0.01):
         super().__init__()
         self.n_flows, self.f_n_features, self.g_n_features = n_flows, f_n_features, g_n_features
@@ -25,6 +25,7 @@ class LocalCondRNVPDecoder(PackedWeights, nn.Module):
             for i in range(n_flows)])
         self.precision = None          # None -> engine.DEFAULT_PRECISION ("f16x3")
         self.materialize_lists = True  # False: skip the 3 x L per-layer tensors (lists then hold the final layer only)
+        # eval_autograd (flows.EvalAutograd): "torch" (default) | "hip" = eval()-mode calls under autograd on the HIP kernels
 
     def coupling_layers(self):
         """All 3*n_flows CondRealNVPFlow3D modules in DIRECT order."""
@@ -72,6 +73,12 @@ class LocalCondRNVPDecoder(PackedWeights, nn.Module):
         import torch
         if noise is None:
             noise = torch.randn_like(logvar0)                                      # models.py:78
+        if self.eval_autograd == "hip":
+            from .frozen_engine import wants_frozen_hip
+            if wants_frozen_hip(self, stack_spec(self, self.coupling_layers()).all_params, noise, mu0, logvar0, g):
+                # the gradient must reach mu0 / logvar0 / noise: z by tensor ops in front of the node
+                z = noise * torch.exp(0.5 * logvar0) + mu0
+                return (z,) + tuple(self.forward(z, g, mode="direct"))
         fused = (not self.training and noise.is_cuda and not _needs_autograd(noise, mu0, logvar0, g)
                  and noise.dtype == torch.float32 and mu0.dtype == torch.float32 and logvar0.dtype == torch.float32)
         if not fused:
@@ -96,6 +103,13 @@ class LocalCondRNVPDecoder(PackedWeights, nn.Module):
                 layers = layers[:int(n_layers)]
             ps, mus, lvs = train_stack(self, layers, p, g, mode, allow_flat=n_layers is None)
             return ps, mus, lvs
+        if self.eval_autograd == "hip":
+            layers = self.coupling_layers()
+            if n_layers is not None:
+                layers = layers[:int(n_layers)]
+            out = frozen_stack(self, self.stack, layers, p, g, mode, self.precision)
+            if out is not None:
+                return out
         if self.training or _needs_autograd(p, g):
             if n_layers is not None:
                 raise ValueError("n_layers is only supported on the fused eval path")

@@ -72,6 +72,7 @@ class FlowStack:
         self._sentinel_state = None
         self._f16_bound = None
         self.last_precision = None
+        self.last_packed = self.last_film = None        # the buffers of the last run (frozen_engine's backward reads them)
         for lyr in (self.layers[0], self.layers[-1]):
             self._sentinels += [lyr.T_mu_0[3].weight, lyr.T_logvar_1[1].weight]
 
@@ -170,10 +171,12 @@ class FlowStack:
                 raise ValueError("n_layers out of range")
             canon, meta, packed, G, precision = self._ensure(precision, p.device, L)
             self.last_precision = precision
+            self.last_packed = packed
             if g.shape[1] != G:
                 raise RuntimeError("g has %d features, the layers expect %d" % (g.shape[1], G))
             dev = p.device
             film = torch.empty(lib().dpf_flow_film_floats(L, B), dtype=torch.float32, device=dev)
+            self.last_film = film
             p_out = torch.empty_like(p)
             sum_lv = torch.empty_like(p)
             pm = torch.empty((B, N, 3), dtype=torch.float32, device=dev) if want_pointmajor else None

@@ -41,6 +41,40 @@ def stack_spec(owner, layers):
     return spec
 
 
+class EvalAutograd:
+    """Mixin: the `eval_autograd` attribute (extension, beside `precision`).  "torch" (default): an eval()-mode call whose inputs
+    require grad is served by tensor operations, with an EvalModeAutogradWarning (layers._needs_autograd).  "hip": an eval()-mode
+    call on CUDA fp32 tensors where p, g or ANY parameter requires grad is one autograd node over the HIP kernels with frozen
+    BatchNorm statistics (networks/frozen_engine.py), no warning.  Setting it on a decoder or a triple reaches the layers."""
+    _eval_autograd = "torch"
+
+    @property
+    def eval_autograd(self):
+        return self._eval_autograd
+
+    @eval_autograd.setter
+    def eval_autograd(self, value):
+        from .frozen_engine import check_eval_autograd
+        self.__dict__["_eval_autograd"] = check_eval_autograd(value)
+        for child in self.children():
+            for m in (child if isinstance(child, nn.ModuleList) else [child]):
+                if isinstance(m, EvalAutograd):
+                    m.eval_autograd = value
+
+
+def frozen_stack(owner, stack, layers, p, g, mode, precision):
+    """(ps, mus, lvs) of `layers` through the frozen-statistics HIP node when the call qualifies (eval_autograd == "hip", CUDA fp32,
+    something requires grad, the f16x3 stack), else None: the caller goes on as with "torch"."""
+    from .frozen_engine import wants_frozen_hip, run_frozen_stack, frozen_precision_ok
+    spec = stack_spec(owner, layers)
+    if not wants_frozen_hip(owner, spec.all_params, p, g):
+        return None
+    stack = stack()
+    if not frozen_precision_ok(stack, spec, precision, p.device):
+        return None
+    return run_frozen_stack(stack, spec, p, g, mode, precision)
+
+
 def train_stack(owner, layers, p, g, mode, allow_flat=False):
     """Run `layers` (DIRECT order) through the HIP training path.  allow_flat: DPF_TRAIN_FLAT=1 may move the
     parameters into a flat store on first use (the decoder passes it for its full stack only)."""
@@ -51,7 +85,7 @@ def train_stack(owner, layers, p, g, mode, allow_flat=False):
     return run_training_stack(spec, p, g, mode)
 
 
-class CondRealNVPFlow3D(PackedWeights, nn.Module):
+class CondRealNVPFlow3D(EvalAutograd, PackedWeights, nn.Module):
     def __init__(self, f_n_features, g_n_features, weight_std=0.01, warp_inds=[0],
                  centered_translation=False, eps=1e-6):
         super().__init__()
@@ -118,13 +152,17 @@ class CondRealNVPFlow3D(PackedWeights, nn.Module):
         if use_hip_training(self, p):
             ps, mus, lvs = train_stack(self, [self], p, g, mode)
             return ps[0], mus[0], lvs[0]
+        if self.eval_autograd == "hip":
+            out = frozen_stack(self, lambda: self.packed_stack(lambda: FlowStack([self])), [self], p, g, mode, self.precision)
+            if out is not None:
+                return out[0][0], out[1][0], out[2][0]
         if self.training or _needs_autograd(p, g):
             return self.forward_torch(p, g, mode)
         p_out, _, ps, mus, lvs = self.packed_stack(lambda: FlowStack([self])).run(p, g, mode, self.precision, want_lists=True)
         return p_out, mus[0], lvs[0]
 
 
-class CondRealNVPFlow3DTriple(nn.Module):
+class CondRealNVPFlow3DTriple(EvalAutograd, PackedWeights, nn.Module):
     WARPS = {0: ([0], [1], [2]), 1: ([0, 1], [0, 2], [1, 2])}     # flows.py:129-148
 
     def __init__(self, f_n_features, g_n_features, weight_std=0.02, pattern=0, centered_translation=False):
@@ -161,4 +199,9 @@ class CondRealNVPFlow3DTriple(nn.Module):
         if use_hip_training(self, p):                              # the three layers as one autograd node
             ps, mus, lvs = train_stack(self, self.layers(), p, g, mode)
             return ps, mus, lvs
+        if self.eval_autograd == "hip":                            # the three layers as one frozen-statistics node
+            out = frozen_stack(self, lambda: self.packed_stack(lambda: FlowStack(self.layers())), self.layers(), p, g, mode,
+                               self.nvp1.precision)
+            if out is not None:
+                return out
         return self._chain(p, g, mode, lambda lyr, pp, gg, mm: lyr(pp, gg, mode=mm))

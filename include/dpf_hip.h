@@ -402,6 +402,32 @@ int dpf_flow_train_backward_lists(int n_layers, int B, int N, int mode, int prec
                                   float *dp_in, float *dp_tmp, float *dcanon, float *dfm,
                                   float flow_eps, void *workspace, dpf_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Eval mode (model.eval(), frozen BatchNorm) under autograd: the backward pass autograd derives from
+ * CondRealNVPFlow3D.forward (flows.py:95-117) when the running statistics normalise (csrc/flow_frozen.hip).  The forward is
+ * dpf_flow_film + dpf_flow_forward with the three per-layer lists, precision DPF_PREC_F16X3 (anything else: DPF_ENOSUP);
+ * `packed` and `film` are the buffers those two calls used -- the backward recomputes each layer from its input with the
+ * forward's own fragments, FiLM blocks and operand split, so the ReLU masks are the forward's.
+ *
+ * tcanon / dcanon: the training-mode block above (L, dpf_flow_train_canon_floats()); dcanon is fully overwritten (zeros in
+ * the padding).  fstats: per layer dpf_flow_frozen_stats_floats() = 512 floats, per branch (logvar, mu)
+ *     running_mean0[64] | running_var0[64] | running_mean1[64] | running_var1[64]
+ * -- inputs, no gradient.  fm / dfm: the FiLM vectors (cw, cb) of this batch and their gradients, per layer
+ * [branch][w|b][B][64]; the per-cloud conditioner nets stay with the caller (frozen BatchNorm there too).
+ * p_in, ps, mus, logvars, the three gradient pointer tables (any table, any entry may be NULL), dp_in, dp_tmp: as
+ * dpf_flow_train_backward_lists.  B >= 1.  Two launches per layer (the layer over its points; its partial rows -> dcanon, dfm),
+ * none per stack, no statistic pass; every sum in a fixed order (no floating-point atomics): repeated calls agree bit for bit.
+ * workspace: dpf_flow_frozen_workspace_bytes(B, N) bytes.  Joins the call-replay cache of the training entries.
+ * ------------------------------------------------------------------------ */
+size_t dpf_flow_frozen_stats_floats(void);
+size_t dpf_flow_frozen_workspace_bytes(int B, int N);
+int dpf_flow_frozen_backward_lists(int n_layers, int B, int N, int mode, int precision, const int *meta_host,
+                                   const float *tcanon, const float *fstats, const void *packed, const float *film,
+                                   const float *fm, const float *p_in, const float *ps, const float *mus,
+                                   const float *logvars, const float *const *g_ps, const float *const *g_mus,
+                                   const float *const *g_lvs, float *dp_in, float *dp_tmp, float *dcanon, float *dfm,
+                                   float flow_eps, void *workspace, dpf_stream_t stream);
+
 /* library identification: returns e.g. "dpf_hip gfx950 r1" */
 const char *dpf_version(void);
 
@@ -584,6 +610,25 @@ int dpf_film_train_backward(int K, int B, int G, const float *g, const float *W0
                             const float *W1, const float *xhat, const float *rstd, const float *dfm, float *dW0,
                             float *dgamma, float *dbeta, float *dW1, float *db1, float *dg_part, int accumulate,
                             dpf_stream_t stream);
+
+/* The same K conditioner nets in eval mode under autograd (frozen BatchNorm: y = (u - running_mean) * rstd * gamma + beta with
+ * rstd = 1 / sqrt(running_var + bn_eps); csrc/film_train.hip, frozen variants of the two kernels above), the companions of
+ * dpf_flow_frozen_backward_lists.  One launch each way; B >= 1; B <= dpf_film_train_max_batch() and G % 4 == 0, else DPF_ENOSUP
+ * (the caller keeps the tensor ops).  running_mean / running_var (K, 64) are inputs and receive no gradient.
+ * forward:  fm (K, B, 64); saved for the backward: xhat (K, B, 64) and rstd (K, 64).
+ * backward: as dpf_film_train_backward without the two mean-correction terms (d u = rstd * gamma * d y), and with d g FINISHED
+ *   in the launch: dg (B, G) or NULL = the sum of the sub-nets' shares over k = 0 .. K - 1 in that order, formed by the workgroup
+ *   that arrives last (no floating-point atomics: repeated calls agree bit for bit).  workspace: dpf_film_frozen_workspace_floats
+ *   floats; ticket: one 32-bit word of device memory that is ZERO before the first call and is left zero by every call (calls
+ *   that share it must be ordered on one stream).  Both may be NULL when dg is. */
+int dpf_film_frozen_forward(int K, int B, int G, const float *g, const float *W0, const float *gamma, const float *beta,
+                            const float *W1, const float *b1, const float *running_mean, const float *running_var,
+                            float bn_eps, float *fm, float *xhat, float *rstd, dpf_stream_t stream);
+size_t dpf_film_frozen_workspace_floats(int K, int B, int G);
+int dpf_film_frozen_backward(int K, int B, int G, const float *g, const float *W0, const float *gamma, const float *beta,
+                             const float *W1, const float *xhat, const float *rstd, const float *dfm, float *dW0,
+                             float *dgamma, float *dbeta, float *dW1, float *db1, float *dg, float *workspace,
+                             unsigned *ticket, int accumulate, dpf_stream_t stream);
 
 #ifdef __cplusplus
 }
