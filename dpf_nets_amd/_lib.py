@@ -93,6 +93,8 @@ SIGNATURES = {
     "dpf_gprior_train_forward": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp]),
     "dpf_gprior_train_backward": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                        _f, _f, _vp]),
+    "dpf_gprior_frozen_workspace_floats": (_sz, [_i, _i, _i, _i]),
+    "dpf_gprior_frozen_backward": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _f] + [_vp] * 10 + [_vp]),
     "dpf_adam_step": (_i, [_sz, _vp, _vp, _vp, _vp, _vp] + [ctypes.c_double] * 7 + [_vp]),
     "dpf_flow_train_update_running": (_i, [_i, ctypes.c_double] + [_vp] * 7),
     "dpf_film_train_max_batch": (_i, []),

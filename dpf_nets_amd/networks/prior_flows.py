@@ -5,10 +5,16 @@ lib/networks/decoders.py:7-38), so reference checkpoints load unchanged.
 forward(g, mode):
   * eval mode, CUDA tensors, no autograd (generation / evaluation): the whole stack in ONE HIP launch
     (csrc/gprior.hip through dpf_gprior_forward); the lists come back as views of three (S,B,G) buffers;
+  * eval mode under autograd (latent optimisation through log p(g), fine-tuning with frozen statistics): with
+    `eval_autograd = "hip"` on the module (flows.EvalAutograd; a container hands it to the modules below it) a call on CUDA
+    fp32 tensors where g OR ANY PARAMETER requires grad is one autograd node -- that same launch forward, two launches
+    backward whatever the number of steps (csrc/gprior_frozen.hip through networks/prior_frozen_engine.py); the BatchNorm
+    buffers are only read and B = 1 is legal.  With the default "torch" a call whose g requires grad is the tensor-op
+    restatement (`forward_torch`) with an EvalModeAutogradWarning, and autograd follows the input only;
   * training mode on CUDA tensors (GlobalRNVPDecoder): BatchNorm on the statistics of the B rows and the whole
     backward through csrc/gprior_train.hip -- one autograd node, 4 launches per step forward and 5 backward instead
     of ~75 tensor-op launches; DPF_TRAIN_IMPL=torch selects the tensor-op restatement (`forward_torch`), which is
-    also what CPU tensors, eval mode under autograd and single RealNVPFlow / RealNVPFlowCouple modules get.
+    also what CPU tensors and single RealNVPFlow / RealNVPFlowCouple modules in train() mode get.
 The kernels know RealNVPFlowCouple's two index patterns (even/odd, halves) on an even G; a RealNVPFlow with
 other warp_inds runs as tensor ops."""
 import ctypes
@@ -22,6 +28,7 @@ from .layers import Swish, PackedWeights, weight_state, _needs_autograd
 from .flat_store import ParamStore
 from .flowlist import FlowList, tag_layer_sum
 from .train_engine import update_running_stats
+from .flows import EvalAutograd
 from .._lib import lib, check, current_stream, MODE
 
 
@@ -37,7 +44,7 @@ def pattern_code(warp_inds, G):
     return None
 
 
-class RealNVPFlow(PackedWeights, nn.Module):
+class RealNVPFlow(EvalAutograd, PackedWeights, nn.Module):
     def __init__(self, n_features, g_n_features, weight_std=0.01, warp_inds=[0], eps=1e-6):
         super().__init__()
         self.n_features = n_features
@@ -83,13 +90,16 @@ class RealNVPFlow(PackedWeights, nn.Module):
     def forward(self, g, mode="direct"):
         if mode not in ("direct", "inverse"):
             raise ValueError(mode)
+        out = _frozen_prior(self, [self], g, mode)
+        if out is not None:
+            return out[0][0], out[1][0], out[2][0]
         if _fusable(self, [self], g):
             _, _, gs, mus, lvs = self.packed_stack(lambda: GPriorStack([self])).run(g, mode)
             return gs[0], mus[0], lvs[0]
         return self.forward_torch(g, mode)
 
 
-class RealNVPFlowCouple(PackedWeights, nn.Module):
+class RealNVPFlowCouple(EvalAutograd, PackedWeights, nn.Module):
     def __init__(self, n_features, g_n_features, weight_std=0.01, pattern=0):
         super().__init__()
         self.n_features = n_features
@@ -123,13 +133,16 @@ class RealNVPFlowCouple(PackedWeights, nn.Module):
     def forward(self, g, mode="direct"):
         if mode not in ("direct", "inverse"):
             raise ValueError(mode)
+        out = _frozen_prior(self, self.layers(), g, mode) if hasattr(self, "nvp1") else None
+        if out is not None:
+            return out
         if _fusable(self, self.layers(), g):
             _, _, gs, mus, lvs = self.packed_stack(lambda: GPriorStack(self.layers())).run(g, mode)
             return list(gs.unbind(0)), list(mus.unbind(0)), list(lvs.unbind(0))
         return self.forward_torch(g, mode)
 
 
-class GlobalRNVPDecoder(PackedWeights, nn.Module):
+class GlobalRNVPDecoder(EvalAutograd, PackedWeights, nn.Module):
     def __init__(self, n_flows, n_features, g_n_features, weight_std=0.01):
         super().__init__()
         self.n_flows = n_flows
@@ -179,6 +192,9 @@ class GlobalRNVPDecoder(PackedWeights, nn.Module):
         if mode not in ("direct", "inverse"):
             raise ValueError(mode)
         steps = self.__dict__.get("_steps") or self.__dict__.setdefault("_steps", self.coupling_layers())
+        out = _frozen_prior(self, steps, g, mode)
+        if out is not None:
+            return out
         if self.n_flows and _fusable(self, steps, g):
             _, sum_lv, gs, mus, lvs = self.stack().run(g, mode)
             return FlowList(gs), FlowList(mus), FlowList(lvs, sum_lv)
@@ -200,9 +216,55 @@ def _patterns_ok(module, layers):
 
 def _fusable(module, layers, g):
     """Eval mode on a CUDA tensor without autograd, every step one of the kernel's index patterns."""
-    if module.training or not g.is_cuda or _needs_autograd(g):      # as the point decoder: autograd follows the INPUT
+    if module.training:
+        return False
+    if not g.is_cuda:
+        if module.eval_autograd == "hip":                           # the HIP node was asked for and is not what serves the call
+            _needs_autograd(g)
+        return False
+    if _needs_autograd(g):                                          # as the point decoder: autograd follows the INPUT
         return False
     return _patterns_ok(module, layers)
+
+
+def _stack_plan(module, layers):
+    """What the training and the frozen-statistics nodes need of a stack, once per module: (parameters, their slots in the
+    canonical block, the BatchNorm modules, the block's floats, the kernel's step codes, (S, G, nf), RealNVPFlow's eps)."""
+    plan = module.__dict__.get("_train_plan")
+    if plan is None:
+        params, slots, bns, total = _step_params(layers)
+        S, G, nf = len(layers), layers[0].g_n_features, layers[0].n_features
+        codes = (ctypes.c_int * S)(*[pattern_code(l.warp_inds, G) for l in layers])
+        assert total == S * lib().dpf_gprior_canon_floats(G, nf)
+        plan = module.__dict__["_train_plan"] = (params, slots, bns, total, codes, (S, G, nf), float(layers[0].eps.item()))
+    return plan
+
+
+def _frozen_prior(module, layers, g, mode):
+    """(gs, mus, lvs) of `layers` (DIRECT order) through the frozen-statistics HIP node when the call qualifies -- eval_autograd ==
+    "hip", eval mode, a CUDA fp32 g, grad enabled, g or any parameter of the stack requires grad, the kernel's index patterns --
+    else None: the caller goes on as with "torch".  Three python lists as the training path returns them."""
+    if module.eval_autograd != "hip" or module.training or not layers or not g.is_cuda or g.dtype != torch.float32 \
+            or not torch.is_grad_enabled() or not _patterns_ok(module, layers):
+        return None
+    from .frozen_engine import wants_frozen_hip
+    from .prior_frozen_engine import run_frozen_prior
+    params, slots, bns, total, codes, dims, eps = _stack_plan(module, layers)
+    if not wants_frozen_hip(module, lambda: params, g):
+        return None
+    if g.dim() != 2 or g.shape[1] != dims[1]:
+        raise RuntimeError("expected g (B,%d)" % dims[1])
+    stack = module.packed_stack(lambda: GPriorStack(layers))
+    store = None
+    if any(t.requires_grad for t in params):
+        # fine-tuning: an optimizer may have moved the parameters behind the version counters' back (updates through .data),
+        # so whatever is packed is refreshed on every call (frozen_engine.frozen_precision_ok is the precedent)
+        stack.refresh_weights()
+        store = module.__dict__.get("_flat")
+        if store is not None and not store.attached():           # .to()/.cuda()/.float() re-assigned the parameters' data
+            store = module.__dict__["_flat"] = PriorFlatStore(layers, g.device)
+    gs, mus, lvs, sum_lv = run_frozen_prior(stack, store, params, slots, (mode, codes, dims, bns[0].eps, eps), g)
+    return list(gs.unbind(0)), list(mus.unbind(0)), tag_layer_sum(list(lvs.unbind(0)), sum_lv)
 
 
 def _step_params(layers):
@@ -327,14 +389,7 @@ def run_training_prior(module, layers, g, mode):
         raise RuntimeError("expected g (B,%d)" % layers[0].g_n_features)
     if g.shape[0] < 2:
         raise ValueError("Expected more than 1 value per channel when training")      # as nn.BatchNorm1d
-    cache = module.__dict__.get("_train_plan")
-    if cache is None:
-        params, slots, bns, total = _step_params(layers)
-        S, G, nf = len(layers), layers[0].g_n_features, layers[0].n_features
-        codes = (ctypes.c_int * S)(*[pattern_code(l.warp_inds, G) for l in layers])
-        assert total == S * lib().dpf_gprior_canon_floats(G, nf)
-        cache = module.__dict__["_train_plan"] = (params, slots, bns, total, codes, (S, G, nf), float(layers[0].eps.item()))
-    params, slots, bns, total, codes, dims, eps = cache
+    params, slots, bns, total, codes, dims, eps = _stack_plan(module, layers)
     store = module.__dict__.get("_flat")
     if store is not None and not store.attached():               # .to()/.cuda()/.float() re-assigned the parameters' data
         store = module.__dict__["_flat"] = PriorFlatStore(layers, g.device)
@@ -363,12 +418,20 @@ class GPriorStack:
         self.G, self.nf = self.layers[0].g_n_features, self.layers[0].n_features
         self.codes = [pattern_code(l.warp_inds, self.G) for l in self.layers]
         self._packed = None
+        self.canon = None            # the canonical block the packed weights were built from (the frozen backward reads it)
         self._state = None
+        self._eps = None
         self._sentinels = []
         for l in (self.layers[0], self.layers[-1]):
             self._sentinels += [l.T_mu_0[0].weight, l.T_mu_0[1].running_var, l.T_logvar_0[3].weight, l.T_logvar_0[1].running_mean]
 
     def invalidate(self):
+        self._packed = None
+        self._eps = None
+
+    def refresh_weights(self):
+        """Repack on the next run: the parameters may have moved (an optimizer's update through .data); `eps` is a buffer no
+        optimizer touches, so it is not fetched again (that read waits for the device)."""
         self._packed = None
 
     def _ensure(self, device):
@@ -384,8 +447,9 @@ class GPriorStack:
             packed = torch.empty(L_.dpf_gprior_packed_floats(S, self.G, self.nf), dtype=torch.float32, device=device)
             bn = self.layers[0].T_mu_0[1]
             check(L_.dpf_gprior_pack(S, self.G, self.nf, bn.eps, canon.data_ptr(), packed.data_ptr(), current_stream()), "gprior_pack")
-            self._packed, self._state = packed, state
-            self._eps = float(self.layers[0].eps.item())
+            self._packed, self.canon, self._state = packed, canon, state
+            if self._eps is None:
+                self._eps = float(self.layers[0].eps.item())
         return self._packed
 
     def run(self, g, mode, want_lists=True):

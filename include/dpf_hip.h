@@ -581,6 +581,25 @@ int dpf_gprior_train_backward(int n_steps, int B, int G, int n_features, int mod
                               float *dcanon, float *workspace, float bn_eps, float eps,
                               dpf_stream_t stream);
 
+/* ---- latent prior flow, EVAL mode under autograd (FROZEN BatchNorm: the running statistics) ----
+ * the backward of GlobalRNVPDecoder.forward under model.eval() (decoders.py:21-38, flows.py:198-243): the forward is
+ * dpf_gprior_forward itself, this call differentiates it in TWO launches whatever n_steps (a row-parallel walk of the steps
+ * in reverse, then every parameter gradient as a fixed-order sum over the rows; no atomics: bit-reproducible).
+ * n_steps, B, G, n_features, mode, codes, eps as dpf_gprior_forward; B >= 1 (B == 0: returns 0, nothing written).
+ * canon: the parameters in either layout of dpf_gprior_train_* -- params_only == 0: the canonical block of dpf_gprior_pack,
+ *   whose running statistics are read (stats is ignored, may be NULL); params_only != 0: W0 | bn.weight | bn.bias | W1 | b1
+ *   per net, and stats (n_steps, 2 nets, 2, n_features) = running_mean | running_var of every net (mu net, then logvar net).
+ * g (B,G) and the forward's gs, mus, lvs (n_steps,B,G); d_gs, d_mus, d_lvs (n_steps,B,G), each may be NULL (= zeros).
+ * -> dg (B,G) and dcanon (the layout of canon; zeros in any running-statistics slot), both overwritten.
+ * workspace: dpf_gprior_frozen_workspace_floats(n_steps, B, G, n_features) fp32, caller-owned; the call never allocates or
+ * synchronises.  Bad arguments (odd G, unknown step code, B < 0, a missing required pointer) return DPF_EINVAL and launch nothing. */
+size_t dpf_gprior_frozen_workspace_floats(int n_steps, int B, int G, int n_features);
+int dpf_gprior_frozen_backward(int n_steps, int B, int G, int n_features, int mode, const int *codes,
+                               int params_only, const float *canon, const float *stats, float bn_eps, float eps,
+                               const float *g, const float *gs, const float *mus, const float *lvs,
+                               const float *d_gs, const float *d_mus, const float *d_lvs, float *dg,
+                               float *dcanon, float *workspace, dpf_stream_t stream);
+
 /* BatchNorm running statistics after a training-mode forward (nn.BatchNorm1d: running = (1 - momentum) * running +
  * momentum * batch, unbiased batch variance; lib/networks/flows.py:27,30,35,42 in train()): all 8 n_layers BatchNorm1d layers
  * of the stack in one launch.  running_mean / running_var (8 n_layers, 64) and num_batches_tracked (8 n_layers, int64): rows
