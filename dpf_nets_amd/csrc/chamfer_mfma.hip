@@ -136,7 +136,12 @@ struct MDir {
 // agent-scope loads, adds them in tile order, writes cd and resets the ticket (tickets are zero on entry and on exit).
 // Payload and ticket go through device-coherent accesses on both sides (MI355X_MICROARCH.md, "valid forms"): per-XCD L2s
 // are not coherent with each other and a plain load could be served a stale line of the previous launch's sums.
-struct MArgs { MDir d[2]; int pn2; float *part; unsigned *ticket; float *cd; };
+struct MArgs {
+    MDir d[2]; int pn2; float *part; unsigned *ticket; float *cd;
+#ifdef DPF_PROFILE
+    unsigned long long *prof;
+#endif
+};
 
 __device__ __forceinline__ f32x16 mfma(uint4 a, uint4 b) {
     const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -210,13 +215,44 @@ __device__ __forceinline__ void exact_tile_mk(P cp, int nc, int t, int tl, int h
 #pragma unroll
     for (int r = 3; r < 15; r += 2) m = fminf(fminf(m, d[r]), d[r + 1]);
     m = fminf(m, d[15]);
-    kmin = INT_MAX;
+    // the lowest row attaining the minimum (descending scan, last hit wins: a compare and a select per row), then ITS index
+    // against nc once: k grows with the row, so if the lowest such row is padding (k >= nc) every other one is too
+    int rmin = 16;
 #pragma unroll
-    for (int r = 15; r >= 0; --r) {
-        const int k = t * 32 + 8 * (r >> 2) + 4 * h + (r & 3);
-        kmin = (d[r] == m && k < nc) ? k : kmin;
-    }
+    for (int r = 15; r >= 0; --r) rmin = d[r] == m ? r : rmin;
+    const int k = t * 32 + 8 * (rmin >> 2) + 4 * h + (rmin & 3);
+    kmin = (rmin < 16 && k < nc) ? k : INT_MAX;
 }
+
+// Wave-wide integer scan / maximum on the DPP path (row shifts, then the two row broadcasts): six VALU instructions each and no
+// LDS round trip, where __shfl_up / __shfl_xor are a ds_bpermute + wait + select per step.  Integers only: the float reductions
+// of this file (mu, the workgroup's sum) have a fixed order of additions and stay butterflies.
+template <int CTRL, int ROW_MASK = 0xF>
+__device__ __forceinline__ unsigned dpp_or0(unsigned v) {      // lanes without a source (and rows outside ROW_MASK) read 0
+    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, true);
+}
+__device__ __forceinline__ unsigned wave_scan_add(unsigned v) {    // inclusive prefix sum over the 64 lanes
+    v += dpp_or0<0x111>(v); v += dpp_or0<0x112>(v); v += dpp_or0<0x114>(v); v += dpp_or0<0x118>(v);    // row_shr:1 2 4 8
+    v += dpp_or0<0x142, 0xA>(v);                                                                       // row_bcast:15 -> rows 1, 3
+    v += dpp_or0<0x143, 0xC>(v);                                                                       // row_bcast:31 -> rows 2, 3
+    return v;
+}
+__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {     // maximum of the 64 lanes, wave-uniform
+    v = max(v, dpp_or0<0x111>(v)); v = max(v, dpp_or0<0x112>(v)); v = max(v, dpp_or0<0x114>(v)); v = max(v, dpp_or0<0x118>(v));
+    v = max(v, dpp_or0<0x142, 0xA>(v));
+    v = max(v, dpp_or0<0x143, 0xC>(v));
+    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// -DDPF_PROFILE builds (make prof; tools/nnm_phase_prof.py): s_memtime at the phase edges of nnm_kernel, written by lane 0 of
+// every wave of a few workgroups to prof[workgroup][wave][16].  The default build has none of it.
+#ifdef DPF_PROFILE
+#define DPF_T(i) { __builtin_amdgcn_sched_barrier(0); \
+    if (prof_at != nullptr) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if ((threadIdx.x & 63) == 0) prof_at[i] = t_; } \
+    __builtin_amdgcn_sched_barrier(0); }
+#else
+#define DPF_T(i)
+#endif
 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void glb_void;
@@ -228,10 +264,8 @@ typedef __attribute__((address_space(1))) const void glb_void;
 template <int QW>
 __global__ __launch_bounds__(QW * 64) void nnm_kernel(MArgs args) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    uint4 *sfrag = (uint4 *)lds;                                  // [CT][64]
-    float *spts = (float *)(lds + NNM_PTS);                        // [CT][PROW]
     unsigned char *qtile = (unsigned char *)(lds + NNM_LISTS);     // [QW][WCAP] 8-byte results of the wave-wide work list
-    __shared__ float s_r2[QW];
+    __shared__ float s_r2[QW], s_sum[QW];
     const bool pairwise = args.pn2 > 0;
     const int dir = pairwise ? (int)(blockIdx.z & 1) : (int)blockIdx.z;
     const MDir A = args.d[dir];
@@ -254,9 +288,19 @@ __global__ __launch_bounds__(QW * 64) void nnm_kernel(MArgs args) {
         if (old == nwg2 - 1) {
             const float *p = args.part + unit * nwg2;
             float s1 = 0.f, s2 = 0.f;
-            for (unsigned x = 0; x < gridDim.x; ++x) {
-                s1 += __hip_atomic_load(&p[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                s2 += __hip_atomic_load(&p[gridDim.x + x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            // eight loads in flight, then their additions in tile order: the order of the sums is what it was, the round
+            // trips are one per four tiles instead of one per tile
+            for (unsigned x0 = 0; x0 < gridDim.x; x0 += 4) {
+                float v1[4], v2[4];
+#pragma unroll
+                for (unsigned u = 0; u < 4; ++u) {
+                    const unsigned x = min(x0 + u, gridDim.x - 1);
+                    v1[u] = __hip_atomic_load(&p[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    v2[u] = __hip_atomic_load(&p[gridDim.x + x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+#pragma unroll
+                for (unsigned u = 0; u < 4; ++u)
+                    if (x0 + u < gridDim.x) { s1 += v1[u]; s2 += v2[u]; }
             }
             args.cd[unit] = s1 / (float)args.d[0].nq + s2 / (float)args.d[1].nq;
             __hip_atomic_store(&args.ticket[unit], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -268,6 +312,12 @@ __global__ __launch_bounds__(QW * 64) void nnm_kernel(MArgs args) {
     }
     const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+#ifdef DPF_PROFILE
+    unsigned long long *prof_at = nullptr;
+    if (args.prof != nullptr && blockIdx.y < 2 && blockIdx.z == 0 && gridDim.x <= 4)
+        prof_at = args.prof + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * QW + wave) * 16;
+#endif
+    DPF_T(0)
     const int qt = blockIdx.x * QW + wave;                                   // query tile of this wave
     const int nqt = tiles_of(nq), nct = tiles_of(nc);
     const bool wave_live = qt < nqt;
@@ -277,6 +327,18 @@ __global__ __launch_bounds__(QW * 64) void nnm_kernel(MArgs args) {
     const int j = qt * 32 + (lane & 31);
     const float *qsrc = A.q + qcloud + (size_t)min(j, nq - 1) * 3;
     const float qx = qsrc[0], qy = qsrc[1], qz = qsrc[2];
+    // The candidates this thread builds fragments of in the first pass (two per thread in the 16-wave form): their loads are
+    // issued HERE, together with the query's and the mu sample's, so that the workgroup -- alone on its CU, all of its waves
+    // in the same phase -- waits for one round trip to memory in its prologue instead of one per dependent load.
+    constexpr int KPT = CT * 32 / (QW * 64);
+    const int npass = (nct + CT - 1) / CT;
+    float px[KPT], py[KPT], pz[KPT];
+#pragma unroll
+    for (int k = 0; k < KPT; ++k) {
+        const int p = tid + k * QW * 64;
+        px[k] = 0.f; py[k] = 0.f; pz[k] = 0.f;
+        if (p < nc) { const float *src = cpts + (size_t)p * 3; px[k] = src[0]; py[k] = src[1]; pz[k] = src[2]; }
+    }
     // The surrogate is evaluated on coordinates translated by mu = the mean of the first 64 candidates (every wave
     // computes the same value: no barrier), so that R2 -- and with it the filter's tolerance tau -- scales with the
     // extent of the data, not with its distance from the origin (an uncentred cloud made every pair a "near tie").
@@ -300,6 +362,7 @@ __global__ __launch_bounds__(QW * 64) void nnm_kernel(MArgs args) {
     const float INF_ = __builtin_inff();
     float r2 = j < nq ? (qcx * qcx + qcy * qcy) + qcz * qcz : 0.f;
     r2 = nn_not_finite(r2) ? INF_ : r2;
+    DPF_T(1)
     if (nct > CT)
         for (int p = tid; p < nc; p += QW * 64) {
             const float *src = cpts + (size_t)p * 3;
@@ -307,51 +370,73 @@ __global__ __launch_bounds__(QW * 64) void nnm_kernel(MArgs args) {
             const float cn = (x * x + y * y) + z * z;
             r2 = nn_not_finite(cn) ? INF_ : fmaxf(r2, cn);
         }
-    float tau = 0.f;
-    bool slow = false;
+
+    uint4 *sfrag = (uint4 *)lds;                                  // [CT][64]
+    float *spts = (float *)(lds + NNM_PTS);                        // [CT][PROW]
+    // fragment rows and packed point of local candidate pl (tile pl >> 5) of a pass; returns |c - mu|^2
+    auto put = [&](int pl, bool live, float x, float y, float z) {
+        const int t = pl >> 5, i = pl & 31;
+        uint4 f0, f1;
+        const float cx = live ? x - mux : 0.f, cy = live ? y - muy : 0.f, cz = live ? z - muz : 0.f;
+        cand_fragment(cx, cy, cz, live, f0, f1);
+        sfrag[t * 64 + i] = f0;
+        sfrag[t * 64 + 32 + i] = f1;
+        // original coordinates for the exact evaluation; padding far away (its distance is +inf)
+        spts[t * PROW + i] = live ? x : 3.0e38f; spts[t * PROW + 32 + i] = live ? y : 3.0e38f; spts[t * PROW + 64 + i] = live ? z : 3.0e38f;
+        return (cx * cx + cy * cy) + cz * cz;
+    };
+    // the first pass, from the registers loaded above; R2's candidate term rides on it
+    {
+        const int tn = min(CT, nct);
+        int tidp = tid;                    // opaque: the build's LDS addresses are made here, per pass, not carried through the sweep
+        asm volatile("" : "+v"(tidp));
+#pragma unroll
+        for (int k = 0; k < KPT; ++k) {
+            const int pl = tidp + k * QW * 64;
+            if ((pl >> 5) < tn) {
+                const float cn = put(pl, pl < nc, px[k], py[k], pz[k]);
+                r2 = nn_not_finite(cn) ? INF_ : fmaxf(r2, cn);
+            }
+        }
+    }
+    DPF_T(2)
+    // R2 of the wave on the DPP path: r2 is a non-negative number or +inf (never NaN, never -0), and those order as their bits
+    const float r2w = u2f(wave_max_u32(f2u(r2)));
+    if (lane == 0) s_r2[wave] = r2w;
+    __syncthreads();                                                          // fragments, points and R2 are published
+    float tau;
+    bool slow;
+    {
+        float m = s_r2[0];
+#pragma unroll
+        for (int w = 1; w < QW; ++w) m = fmaxf(m, s_r2[w]);
+        tau = m * 2.44140625e-4f;                                             // 2^-12 * R2
+        slow = nn_not_finite(m);                                              // workgroup-uniform: m comes from LDS
+    }
+    DPF_T(3)
 
     unsigned short *wl = (unsigned short *)(lds + NNM_LISTS + QW * SCH * 64) + (size_t)wave * WCAP;      // (source lane << 8) | tile
     uint2 *res = (uint2 *)(qtile + (size_t)wave * SCH * 64);       // (distance bits, index) per work item of the wave
     float smin = __builtin_inff();
     float best = __builtin_inff();
     int bidx = INT_MAX;
-    const int npass = (nct + CT - 1) / CT;
-    for (int pass = 0; pass < npass; ++pass) {
+    for (int pass = 0; pass < (slow ? 0 : npass); ++pass) {
         const int t0 = pass * CT, tn = min(CT, nct - t0);
-        if (pass > 0) __syncthreads();                                        // everyone is done with the previous pass
-        int tidp = tid;                    // opaque: the build's LDS addresses are made here, per pass, not carried through the sweep
-        asm volatile("" : "+v"(tidp));
+        if (pass > 0) {
+            __syncthreads();                                                  // everyone is done with the previous pass
+            int tidp = tid;
+            asm volatile("" : "+v"(tidp));
 #pragma unroll
-        for (int k = 0; k < CT * 32 / (QW * 64); ++k) {                       // two candidates per thread
-            const int pl = tidp + k * QW * 64, t = pl >> 5, i = pl & 31, p = t0 * 32 + pl;
-            if (t < tn) {
-                const bool live = p < nc;
-                float x = 0.f, y = 0.f, z = 0.f;
-                if (live) { const float *src = cpts + (size_t)p * 3; x = src[0]; y = src[1]; z = src[2]; }
-                uint4 f0, f1;
-                const float cx = live ? x - mux : 0.f, cy = live ? y - muy : 0.f, cz = live ? z - muz : 0.f;
-                cand_fragment(cx, cy, cz, live, f0, f1);
-                sfrag[t * 64 + i] = f0;
-                sfrag[t * 64 + 32 + i] = f1;
-                // original coordinates for the exact evaluation; padding far away (its distance is +inf)
-                spts[t * PROW + i] = live ? x : 3.0e38f; spts[t * PROW + 32 + i] = live ? y : 3.0e38f; spts[t * PROW + 64 + i] = live ? z : 3.0e38f;
-                if (pass == 0) {
-                    const float cn = (cx * cx + cy * cy) + cz * cz;
-                    r2 = nn_not_finite(cn) ? INF_ : fmaxf(r2, cn);
+            for (int k = 0; k < KPT; ++k) {
+                const int pl = tidp + k * QW * 64, p = t0 * 32 + pl;
+                if ((pl >> 5) < tn) {
+                    const bool live = p < nc;
+                    float x = 0.f, y = 0.f, z = 0.f;
+                    if (live) { const float *src = cpts + (size_t)p * 3; x = src[0]; y = src[1]; z = src[2]; }
+                    put(pl, live, x, y, z);
                 }
             }
-        }
-        if (pass == 0) {
-            for (int d = 32; d > 0; d >>= 1) r2 = fmaxf(r2, __shfl_xor(r2, d));
-            if (lane == 0) s_r2[wave] = r2;
-        }
-        __syncthreads();                                                      // fragments and points are published
-        if (pass == 0) {
-            float m = s_r2[0];
-#pragma unroll
-            for (int w = 1; w < QW; ++w) m = fmaxf(m, s_r2[w]);
-            tau = m * 2.44140625e-4f;                                         // 2^-12 * R2
-            if (nn_not_finite(m)) { slow = true; break; }                     // workgroup-uniform: m comes from LDS
+            __syncthreads();                                                  // fragments and points are published
         }
         if (wave_live) {
             // r04: the sweep keeps NO queue.  r01-r03 visited every tile with the running minimum (a hit test, a head in
@@ -419,6 +504,7 @@ __global__ __launch_bounds__(QW * 64) void nnm_kernel(MArgs args) {
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
+                DPF_T(4 + 5 * (c0 / SCH))
                 float cm = fminf(fminf(mt[0], mt[1]), mt[2]);
 #pragma unroll
                 for (int u = 3; u + 1 < SCH; u += 2) cm = fminf(fminf(cm, mt[u]), mt[u + 1]);
@@ -426,36 +512,45 @@ __global__ __launch_bounds__(QW * 64) void nnm_kernel(MArgs args) {
                 smin = fminf(smin, cm);
                 const float thr = fminf(smin, __shfl_xor(smin, 32)) + tau;
                 // the lane's survivors as a bit mask (tile u at bit SCH - 1 - u): a compare and a shift-or per tile, no list
+                // smask = 2 smask + (mt[u] <= thr) per tile: a compare and an add-with-carry (the compiler's own form is compare,
+                // select, shift, or).  Sixteen tiles per asm statement (the operand limit is 30): one statement per tile had the
+                // compiler put a wait state between every two of them
                 unsigned smask = 0;
+                static_assert(SCH == 32, "the mask is built sixteen tiles at a time, twice");
+#define NNM_MK(n) "v_cmp_le_f32 vcc, %" #n ", %17\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
 #pragma unroll
-                for (int u = 0; u < SCH; ++u)          // smask = 2 smask + (mt[u] <= thr): a compare and an add-with-carry (the compiler's
-                                                       // own form is compare, select, shift, or)
-                    asm("v_cmp_le_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(smask) : "v"(mt[u]), "v"(thr) : "vcc");
+                for (int u = 0; u < SCH; u += 16)
+                    asm(NNM_MK(1) NNM_MK(2) NNM_MK(3) NNM_MK(4) NNM_MK(5) NNM_MK(6) NNM_MK(7) NNM_MK(8)
+                        NNM_MK(9) NNM_MK(10) NNM_MK(11) NNM_MK(12) NNM_MK(13) NNM_MK(14) NNM_MK(15) NNM_MK(16)
+                        : "+v"(smask)
+                        : "v"(mt[u]), "v"(mt[u + 1]), "v"(mt[u + 2]), "v"(mt[u + 3]), "v"(mt[u + 4]), "v"(mt[u + 5]), "v"(mt[u + 6]),
+                          "v"(mt[u + 7]), "v"(mt[u + 8]), "v"(mt[u + 9]), "v"(mt[u + 10]), "v"(mt[u + 11]), "v"(mt[u + 12]),
+                          "v"(mt[u + 13]), "v"(mt[u + 14]), "v"(mt[u + 15]), "v"(thr)
+                        : "vcc");
+#undef NNM_MK
                 // (a ragged last chunk repeated its last tile in slots cn .. SCH - 1: those bits name tiles that are not there)
                 if (cn < SCH) smask &= ~0u << (SCH - cn);
                 const int nsurv = __builtin_popcount(smask);
-                int smax = nsurv;
-                for (int d = 32; d > 0; d >>= 1) smax = max(smax, __shfl_xor(smax, d));
-                smax = __builtin_amdgcn_readfirstlane(smax);
+                DPF_T(5 + 5 * (c0 / SCH))
                 // Exact evaluation.  A lane has 1-2 survivors per chunk on average but the wave's maximum is ~4, and a
                 // round of the per-lane loop costs a whole exact_tile for every lane: instead the wave's survivors go into
                 // ONE lane-major work list (exclusive scan of the counts), 64 items are evaluated per round by whichever
                 // lane comes -- the owner's query arrives by shuffle -- and the owners merge their own results under the
                 // (d, index) rule, which does not care about order.  (An adversarial chunk with more than WCAP items keeps
-                // the per-lane loop.)
-                int off = nsurv;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(off, d); off += lane >= d ? v : 0; }
+                // the per-lane loop.)  The scan is six DPP additions; the list is written and merged for as many rounds as SOME
+                // lane has survivors (a ballot per round: no wave-wide maximum is taken for it).
+                int off = (int)wave_scan_add((unsigned)nsurv);
                 const int W = __builtin_amdgcn_readlane(off, 63);
                 off -= nsurv;
                 if (W <= WCAP) {
                     {
                         unsigned mk = smask;
-                        for (int e = 0; e < smax; ++e) {
+                        for (int e = 0; __builtin_amdgcn_ballot_w64(mk != 0) != 0; ++e) {
                             if (mk != 0) wl[off + e] = (unsigned short)((lane << 8) | (SCH - 1 - __builtin_ctz(mk)));
                             mk &= mk - 1;
                         }
                     }
+                    DPF_T(6 + 5 * (c0 / SCH))
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                     for (int i0 = 0; i0 < W; i0 += 64) {
@@ -469,7 +564,8 @@ __global__ __launch_bounds__(QW * 64) void nnm_kernel(MArgs args) {
                     }
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
-                    for (int e = 0; e < smax; ++e) {
+                    DPF_T(7 + 5 * (c0 / SCH))
+                    for (int e = 0; __builtin_amdgcn_ballot_w64(e < nsurv) != 0; ++e) {
                         if (e < nsurv) {
                             const uint2 r = res[off + e];
                             const float m = __uint_as_float(r.x);
@@ -481,7 +577,9 @@ __global__ __launch_bounds__(QW * 64) void nnm_kernel(MArgs args) {
                     }
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();                      // the results' space is the next chunk's
+                    DPF_T(8 + 5 * (c0 / SCH))
                 } else {
+                    const int smax = (int)wave_max_u32((unsigned)nsurv);
                     unsigned mk = smask;
                     for (int e = 0; e < smax; ++e) {
                         const bool take = mk != 0;
@@ -514,19 +612,20 @@ __global__ __launch_bounds__(QW * 64) void nnm_kernel(MArgs args) {
         }
         if (!sums) return;
     }
+    DPF_T(14)
     // sum of this workgroup's distances in a fixed order -- butterfly over the 32 queries of a wave, waves in
     // ascending order -- so that the result does not depend on scheduling
     float sum = (wave_live && h == 0 && j_out < nq) ? best : 0.f;
     for (int d = 16; d > 0; d >>= 1) sum += __shfl_xor(sum, d);
-    __syncthreads();                                   // s_r2 is free again (every wave has read tau's inputs long ago)
-    if (lane == 0) s_r2[wave] = sum;
+    if (lane == 0) s_sum[wave] = sum;                  // (its own 64 bytes: no barrier to wait for s_r2's readers)
     __syncthreads();
     if (tid == 0) {
-        float t = s_r2[0];
+        float t = s_sum[0];
 #pragma unroll
-        for (int w = 1; w < QW; ++w) t += s_r2[w];
+        for (int w = 1; w < QW; ++w) t += s_sum[w];
         publish(t);
     }
+    DPF_T(15)
 }
 
 // ---- the filter's surrogate, read back (tests/test_gpu_chamfer.py::test_filter_surrogate_error_bound) -------------------------
@@ -589,6 +688,12 @@ extern "C" size_t dpf_nndistance_mfma_workspace_bytes(int b, int n, int m) {
     return 0;            // the fragments are built inside the kernel since r01; the argument is kept for the ABI
 }
 
+#ifdef DPF_PROFILE
+// profile builds: where nnm_kernel's phase stamps go ((8 workgroups, QW waves, 16) uint64; nullptr = none)
+static unsigned long long *g_nnm_prof = nullptr;
+extern "C" void dpf_debug_set_nnm_prof(void *p) { g_nnm_prof = (unsigned long long *)p; }
+#endif
+
 static long nnm_workgroups(int b, int n, int m, int qw) {
     return (long)b * ((n + qw * 32 - 1) / (qw * 32) + (m + qw * 32 - 1) / (qw * 32));
 }
@@ -610,6 +715,9 @@ static int launch_nnm(int b, int n, const float *xyz, long xyz_stride, int m, co
                       bool force16 = false, unsigned *ticket = nullptr, float *cd = nullptr) {
     MArgs ma;
     ma.pn2 = 0; ma.part = part; ma.ticket = ticket; ma.cd = cd;
+#ifdef DPF_PROFILE
+    ma.prof = g_nnm_prof;
+#endif
     ma.d[0] = MDir{xyz, xyz2, result, result_i, n, m, xyz_stride, xyz2_stride};       // nndistance.cu:126
     ma.d[1] = MDir{xyz2, xyz, result2, result2_i, m, n, xyz2_stride, xyz_stride};     // nndistance.cu:127
     const int nmax = n > m ? n : m;
@@ -694,6 +802,9 @@ extern "C" int dpf_pairwise_cd(int n1, int n2, int n, int m, const float *clouds
     const long npairs = (long)n1 * n2;
     hipStream_t s = (hipStream_t)stream;
     ma.pn2 = n2; ma.ticket = (unsigned *)workspace; ma.part = (float *)workspace + npairs; ma.cd = cds;
+#ifdef DPF_PROFILE
+    ma.prof = nullptr;
+#endif
     // the tickets (first n1 * n2 words) start at zero; the last arriver of every pair resets its own
     if (hipError_t e = dpf_zero_async(workspace, (size_t)npairs * sizeof(unsigned), s); e != hipSuccess) return (int)e;
     if (qw == 16) {
