@@ -185,6 +185,7 @@ __global__ __launch_bounds__(T) void prep_kernel(int B, int G, int nf, size_t cn
                                                  const float *__restrict__ gs, const float *__restrict__ mus,
                                                  const float *__restrict__ lvs, const float *__restrict__ h,
                                                  const float *__restrict__ stats, const float *__restrict__ cnet,
+                                                 const float *__restrict__ w1l, const float *__restrict__ b1l,
                                                  float *__restrict__ d_o, float *__restrict__ dnext, float *__restrict__ hs) {
     const int K = G >> 1, e = blockIdx.x * T + threadIdx.x;
     if (e < B * K) {
@@ -197,7 +198,25 @@ __global__ __launch_bounds__(T) void prep_kernel(int B, int G, int nf, size_t cn
         const float dmu = (d_mus ? d_mus[at + wi] : 0.f) + (inverse ? -dw * sc : dw);
         const float dlv = (d_lvs ? d_lvs[at + wi] : 0.f) + (inverse ? -0.5f * dw * out : 0.5f * dw * (out - mu));
         d_o[(size_t)b * 2 * K + i] = dmu;
-        d_o[(size_t)b * 2 * K + K + i] = dlv * (1.f - eps * expf(-lv));          // d/do log(eps + exp(o)) = exp(o) / (eps + exp(o))
+        // d/do log(eps + exp(o)) = exp(o) / (eps + exp(o)) = 1 - eps exp(-lv).  Where the floor is active the second form cancels
+        // (lv is rounded to 5e-7 there, the factor itself may be 1e-3): the factor is then formed from o, which only the forward
+        // had -- recomputed here as sgemm_kernel sums it (per chunk of KC a quarter to each of four partial sums, then pairwise).
+        const float q = eps * expf(-lv);
+        float dlv_do = 1.f - q;
+        if (q > 0.5f) {
+            float part[4] = {0.f, 0.f, 0.f, 0.f};
+            const float *hl = h + (size_t)b * 2 * nf + nf, *wl = w1l + (size_t)i * nf;
+            for (int c0 = 0; c0 < nf; c0 += KC)
+#pragma unroll
+                for (int w = 0; w < 4; ++w)
+                    for (int j = c0 + w * (KC / 4); j < c0 + (w + 1) * (KC / 4) && j < nf; ++j) {
+                        const float rstd = 1.f / sqrtf(stats[3 * nf + j] + bn_eps);
+                        part[w] = fmaf(swish(fmaf((hl[j] - stats[nf + j]) * rstd, cnet[cn + j], cnet[cn + nf + j])), wl[j], part[w]);
+                    }
+            const float eo = expf(((part[0] + part[1]) + (part[2] + part[3])) + b1l[i]);
+            dlv_do = eo / (eps + eo);
+        }
+        d_o[(size_t)b * 2 * K + K + i] = dlv * dlv_do;
         dnext[at + wi] = dw * sc;
         dnext[at + ki] = dk;
     }
@@ -327,11 +346,11 @@ int dpf_gprior_train_backward(int S, int B, int G, int nf, int mode, const int *
         const float *h = save_h + (size_t)s * BH, *stats = save_stats + (size_t)s * 4 * nf;
         float *dnext = t == 0 ? dg : run[t & 1];
         const int n_el = B * K > B * 2 * nf ? B * K : B * 2 * nf;
+        const float *w1 = cs + (size_t)nf * K + (size_t)nbn * nf;
         hipLaunchKernelGGL(prep_kernel, dim3((n_el + T - 1) / T), dim3(T), 0, st, B, G, nf, cn, mode, kmul, kadd, wadd, eps, bn_eps, dcur,
                            d_gs ? d_gs + (size_t)s * BG : nullptr, d_mus ? d_mus + (size_t)s * BG : nullptr,
                            d_lvs ? d_lvs + (size_t)s * BG : nullptr, gs + (size_t)s * BG, mus + (size_t)s * BG, lvs + (size_t)s * BG, h, stats,
-                           cs + (size_t)nf * K, d_o, dnext, hs);
-        const float *w1 = cs + (size_t)nf * K + (size_t)nbn * nf;
+                           cs + (size_t)nf * K, w1 + cn, w1 + (size_t)K * nf + cn, d_o, dnext, hs);
         float *dw1 = dcs + (size_t)nf * K + (size_t)nbn * nf;
         Gemm g1 = {B, nf, K, 1, 0, d_o, w1, dhs, 2L * K, 1, K, 0, nf, 1, (long)cn, 0, 2L * nf, 1, nf};            // d hs = d_o W1
         Gemm g2 = {K, nf, B, 1, 0, d_o, hs, dw1, 1, 2L * K, K, 0, 2L * nf, 1, nf, 0, nf, 1, (long)cn};            // d W1 = d_o^T hs
