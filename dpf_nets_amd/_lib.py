@@ -75,6 +75,10 @@ SIGNATURES = {
     "dpf_encoder_packed_bytes": (_sz, [_i]),
     "dpf_encoder_pack": (_i, [_i, _vp, _vp, _vp]),
     "dpf_encoder_forward": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dpf_encoder_arg_scratch_bytes": (_sz, [_i]),
+    "dpf_encoder_forward_arg": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dpf_encoder_frozen_workspace_bytes": (_sz, [_i]),
+    "dpf_encoder_frozen_backward": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dpf_debug_nn_surrogate": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp]),
     "dpf_debug_emd_exponents": (_i, [_i, _i, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "dpf_train_graph_replays": (_l, []),

@@ -24,38 +24,10 @@
 // global_load_lds, one workgroup barrier per chunk).
 #include "flow_common.h"
 #include "encoder_layout.h"
+#include "encoder_mfma.h"
 #include "zero_fill.h"
 
 namespace {
-
-// packed: [A0 4 KiB: [t2][ks2][lane64][8] | bias 4 KiB: b1acc[4][2][16] b2acc[8][2][16] b3[512] pad | chunks]
-// The fragments of layers 1-3 form one stream of 336 slots (a slot = the NS parts of one 1 KiB fragment):
-// layer 1: 4 M tiles x 4 k-steps at slot 0, layer 2: 8 x 8 at slot 16, layer 3: 16 N tiles x 16 at slot 80; a tile's
-// k-steps are consecutive and never straddle a chunk of e_slots(NS) slots.  Chunk: [part][slot][lane64][8].
-constexpr int EP_A0 = 0, EP_BIAS = 4096, EP_CHUNKS = 8192;
-constexpr int EB_1 = 0, EB_2 = 128, EB_3 = 384;                      // float offsets inside the bias block
-constexpr int ES_L1 = 0, ES_L2 = 16, ES_L3 = 80, ES_TOTAL = 336;
-// slots per chunk: 32 (two 64 KiB buffers at bf16x3) halves the number of workgroup barriers; bf16x6 keeps 16
-__host__ __device__ constexpr int e_slots(int NS) { return NS == 3 ? 16 : 32; }
-__host__ __device__ constexpr int e_nchunk(int NS) { return (ES_TOTAL + e_slots(NS) - 1) / e_slots(NS); }
-__host__ __device__ constexpr int ep_chunk_bytes(int NS) { return NS * e_slots(NS) * 1024; }
-__host__ __device__ constexpr size_t ep_bytes(int NS) { return EP_CHUNKS + (size_t)e_nchunk(NS) * ep_chunk_bytes(NS); }
-
-// A workgroup covers 8 tiles (256 points) of one cloud.  TP = tiles per wave:
-//   TP = 1 (default): 8 waves, two per SIMD with 256 VGPRs each (bf16x6: 4 waves, one per SIMD -- it keeps 192 VGPRs
-//          of layer-3 operand fragments);
-//   TP = 2 (-DDPF_ENC_TP=2; bf16, bf16x3): 4 waves, one per SIMD with 484 VGPRs; every weight fragment read from
-//          LDS feeds the MFMAs of both tiles, halving the LDS->VGPR traffic.  Measured r01 at cfg-2: 56.1 us vs
-//          50.5 us for TP = 1 -- a lone wave per SIMD does not hide its own LDS and MFMA latencies.
-#ifndef DPF_ENC_TP
-#define DPF_ENC_TP 1
-#endif
-__host__ __device__ constexpr int e_tp(int NS) { return NS == 3 ? 1 : DPF_ENC_TP; }
-__host__ __device__ constexpr int e_waves(int NS) { return NS == 3 ? 4 : 8 / e_tp(NS); }
-
-// K index held by element j of lane-half kg in k-step ks = the feature that register 8*(ks&1)+j of accumulator
-// tile ks>>1 holds in lane-half kg (acc_feature)
-__host__ __device__ constexpr int k_feature(int ks, int j, int kg) { return acc_feature(ks >> 1, 8 * (ks & 1) + j, kg); }
 
 template <int NS>
 __global__ __launch_bounds__(256) void enc_pack_kernel(const float *__restrict__ canon, uint8_t *__restrict__ packed) {
@@ -132,100 +104,18 @@ struct EncArgs {
     float *gmax;           // (B,512), zero-initialised by the launcher; updated with integer atomicMax (values >= 0)
     float *feat;           // (B,512,N) or NULL
     int B, N;
+    // ARG variant (dpf_encoder_forward_arg): gmax is NOT zero-initialised and is written once, by the cloud's last workgroup
+    int *arg;                       // (B,512): lowest point attaining gmax
+    unsigned long long *keys;       // (B,512) scratch, zero on entry: (value bits << 32) | (0xFFFFFFFF - point), integer atomic max
+    unsigned *ticket;               // (B) scratch, zero on entry
 };
 
-// relu + split of one accumulator tile into the two k-steps 2t, 2t+1 of the next layer's fragments
-template <int NS>
-__device__ __forceinline__ void relu_split(const f32x16 &acc, u32x4 (&dst)[NS][16], int t) {
-#pragma unroll
-    for (int r = 0; r < 16; r += 2) {
-        const float v0 = relu(acc[r]), v1 = relu(acc[r + 1]);
-        const int s = 2 * t + (r >> 3), d = (r & 7) >> 1;
-        if (NS == 1) {
-            dst[0][s][d] = pack_bf16_rne(v0, v1);
-        } else if (NS == 2) {
-            float l0, l1;
-            split_hi(v0, l0); split_hi(v1, l1);
-            dst[0][s][d] = pack_bf16_trunc(v0, v1);
-            dst[1][s][d] = pack_bf16_rne(l0, l1);
-        } else {
-            float l0, l1, m0, m1;
-            split_hi(v0, l0); split_hi(v1, l1);
-            split_hi(l0, m0); split_hi(l1, m1);
-            dst[0][s][d] = pack_bf16_trunc(v0, v1);
-            dst[1][s][d] = pack_bf16_trunc(l0, l1);
-            dst[2][s][d] = pack_bf16_rne(m0, m1);
-        }
-    }
-}
-
-template <int NS>
-__device__ __forceinline__ void stage_chunk(const uint8_t *packed, int c, uint8_t *lds, int wave, int lane) {
-    constexpr int NI = ep_chunk_bytes(NS) / 1024, EW = e_waves(NS);     // wave-instructions of 1 KiB
-    const uint8_t *src = packed + EP_CHUNKS + (size_t)c * ep_chunk_bytes(NS);
-#pragma unroll
-    for (int i = 0; i < NI / EW; ++i) {
-        const int k = wave + i * EW;
-        __builtin_amdgcn_global_load_lds((glb_void *)(src + k * 1024 + lane * 16), (lds_void *)(lds + k * 1024), 16, 0, 0);
-    }
-}
-
-// One output tile for each of the wave's TP point tiles: K k-steps of fragments at slots [slot0, slot0 + K) of the
-// chunk at cb; every fragment read feeds the MFMAs of all TP tiles.  SWAP: the activations are the A operand and the
-// weights the B operand.  NA accumulators per tile (even / odd k-steps) keep consecutive MFMAs independent.
-template <int NS, int K, bool SWAP, int TP, int NA>
-__device__ __forceinline__ void tile_gemm(const uint8_t *cb, int slot0, int lane, const u32x4 (&act)[TP][NS][16],
-                                          f32x16 (&out)[TP]) {     // out: in = initial value, out = result
-    typedef Terms<NS> TT;
-    f32x16 acc[TP][NA];
-#pragma unroll
-    for (int q = 0; q < TP; ++q) {
-        acc[q][0] = out[q];
-        if (NA == 2) acc[q][NA - 1] = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    }
-    u32x4 wf[2][NS];
-    auto load = [&](int ks, u32x4 (&dst)[NS]) {
-#pragma unroll
-        for (int part = 0; part < NS; ++part)
-            dst[part] = *(const u32x4 *)(cb + part * (e_slots(NS) * 1024) + ((slot0 + ks) * 64 + lane) * 16);
-    };
-    load(0, wf[0]);
-#pragma unroll
-    for (int ks = 0; ks < K; ++ks) {
-        if (ks + 1 < K) load(ks + 1, wf[(ks + 1) & 1]);
-#pragma unroll
-        for (int term = 0; term < TT::N; ++term)
-#pragma unroll
-            for (int q = 0; q < TP; ++q) {
-                const u32x4 w = wf[ks & 1][TT::A[term]], x = act[q][TT::B[term]][ks];
-                f32x16 &d = acc[q][ks & (NA - 1)];
-                d = SWAP ? mfma(x, w, d) : mfma(w, x, d);
-            }
-    }
-    // (element by element through an opaque copy: a vector `+` becomes v_pk_add_f32, which the scheduler then places directly in
-    // front of the next tile's first MFMA -- the one pairing tools/asm_bisect found losing a packed result in csrc/emd.hip's
-    // vectorised build; tools/mfma_overlap_check.py --no-packed-before-mfma gates every object on it)
-#pragma unroll
-    for (int q = 0; q < TP; ++q) {
-        if (NA == 2) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float hi = acc[q][NA - 1][r];
-                asm volatile("" : "+v"(hi));
-                out[q][r] = acc[q][0][r] + hi;
-            }
-        } else {
-            out[q] = acc[q][0];
-        }
-    }
-}
-
-__device__ __forceinline__ float half_max(float x) {   // max(x(lane), x(lane ^ 32))
-    const auto r = __builtin_amdgcn_permlane32_swap(f2u(x), f2u(x), false, false);
-    return fmaxf(u2f(r[0]), u2f(r[1]));
-}
-
-template <int NS>
+// ARG: the max over the points also yields the point that attains it.  A lane tracks (value bits, 255 - point of the wave)
+// of its in-lane maximum as one 64-bit key, the waves of a workgroup meet in LDS, the workgroups of a cloud in a 64-bit
+// integer atomic max -- order-independent, no floating-point atomics -- and the workgroup that arrives last at the cloud's
+// ticket unpacks the keys into gmax and arg.  The values are relu'd on the bit pattern (>= +0), so the keys order like the
+// floats, equal values order by descending point, and gmax has the bits of the plain kernel's result.
+template <int NS, bool ARG>
 __global__ __launch_bounds__(e_waves(NS) * 64) void enc_kernel(EncArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     constexpr int CHB = ep_chunk_bytes(NS), EW = e_waves(NS), TP = e_tp(NS);
@@ -234,6 +124,7 @@ __global__ __launch_bounds__(e_waves(NS) * 64) void enc_kernel(EncArgs a) {
     constexpr int NA12 = (EW == 4 && TP == 1) ? 2 : 1, NA3 = TP == 2 ? 1 : 2;
     uint8_t *l_a0 = smem, *l_bias = smem + 4096, *l_buf = smem + 8192;
     float *l_wmax = (float *)(smem + 8192 + 2 * CHB);             // [EW][512]
+    [[maybe_unused]] uint8_t *l_widx = smem + 8192 + 2 * CHB + EW * EC4 * 4;       // ARG: [EW][512] point of the wave's TP tiles
 
     const int bi = blockIdx.y;
     const int lane = threadIdx.x & 63, h = lane >> 5, pl = lane & 31;
@@ -258,84 +149,22 @@ __global__ __launch_bounds__(e_waves(NS) * 64) void enc_kernel(EncArgs a) {
     __syncthreads();
 
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    // ---- layer 0: 3 -> 64 on the matrix core, fp32-accurate (3-way split of x, y | z)
-    u32x4 f1[TP][NS][16];        // only k-steps 0..3 are used
-#pragma unroll
-    for (int q = 0; q < TP; ++q) {
-        const u32x4 b0 = input_fragment(h ? py[q] : px[q], h);
-        u32x4 b1 = input_fragment(pz[q], 0);
-        if (h) b1 = u32x4{0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const u32x4 a00 = *(const u32x4 *)(l_a0 + ((t * 2 + 0) * 64 + lane) * 16);
-            const u32x4 a01 = *(const u32x4 *)(l_a0 + ((t * 2 + 1) * 64 + lane) * 16);
-            f32x16 acc = mfma(a00, b0, zero16);
-            acc = mfma(a01, b1, acc);
-            relu_split<NS>(acc, f1[q], t);
-        }
-    }
-    auto bias_tile = [&](int off, int mt) {       // accumulator-order shift of M tile mt
-        const float *bp = (const float *)l_bias + off + (mt * 2 + h) * 16;
-        f32x16 v;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 b = *(const f32x4 *)(bp + 4 * q);
-            v[4 * q + 0] = b.x; v[4 * q + 1] = b.y; v[4 * q + 2] = b.z; v[4 * q + 3] = b.w;
-        }
-        return v;
-    };
-    // Chunk `cur` is resident in buffer cur & 1 and chunk cur + 1 is on its way into the other one.  Moving on to the
-    // next chunk is one barrier (it has landed; everybody is done with the buffer the one after it will overwrite).
-    constexpr int S = e_slots(NS), NCH = e_nchunk(NS);
-    int cur = 0;
-    stage_chunk<NS>(a.packed, 1, l_buf + CHB, wave, lane);
-    auto chunk_of = [&](int slot) -> const uint8_t * {       // slot: wave-uniform
-        const int c = slot / S;
-        if (c != cur) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // chunk c's pieces (issued a chunk ago) have landed
-            __syncthreads();
-            cur = c;
-            if (c + 1 < NCH) stage_chunk<NS>(a.packed, c + 1, l_buf + ((c + 1) & 1) * CHB, wave, lane);
-        }
-        return l_buf + (c & 1) * CHB;
-    };
-    // ---- layer 1: 64 -> 128
-    u32x4 f2[TP][NS][16];        // k-steps 0..7
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-        const int slot = ES_L1 + 4 * mt;
-        const uint8_t *cb = chunk_of(slot);
-        f32x16 acc[TP];
-#pragma unroll
-        for (int q = 0; q < TP; ++q) acc[q] = bias_tile(EB_1, mt);
-        tile_gemm<NS, 4, false, TP, NA12>(cb, slot % S, lane, f1, acc);
-#pragma unroll
-        for (int q = 0; q < TP; ++q) relu_split<NS>(acc[q], f2[q], mt);
-    }
-    // ---- layer 2: 128 -> 256
+    constexpr int S = e_slots(NS);
+    EncStream<NS> st{a.packed, l_buf, wave, lane, 0};
     u32x4 f3[TP][NS][16];
-#pragma unroll
-    for (int mt = 0; mt < 8; ++mt) {
-        const int slot = ES_L2 + 8 * mt;
-        const uint8_t *cb = chunk_of(slot);
-        f32x16 acc[TP];
-#pragma unroll
-        for (int q = 0; q < TP; ++q) acc[q] = bias_tile(EB_2, mt);
-        tile_gemm<NS, 8, false, TP, NA12>(cb, slot % S, lane, f2, acc);
-#pragma unroll
-        for (int q = 0; q < TP; ++q) relu_split<NS>(acc[q], f3[q], mt);
-    }
+    enc_layers012<NS, TP, NA12>(st, l_a0, l_bias, lane, px, py, pz, f3, EncNoTap());
     // ---- layer 3: 256 -> 512, operands swapped: accumulator register r = point (r&3) + 8*(r>>2) + 4h of the tile,
     //      lane column = output feature; one 32-feature tile at a time.
     for (int nt = 0; nt < 16; ++nt) {
         const int slot = ES_L3 + 16 * nt;
-        const uint8_t *cb = chunk_of(slot);
+        const uint8_t *cb = st.at(slot);
         f32x16 acc[TP];
 #pragma unroll
         for (int q = 0; q < TP; ++q) acc[q] = zero16;
         tile_gemm<NS, 16, true, TP, NA3>(cb, slot % S, lane, f3, acc);
         const float shift = ((const float *)l_bias)[EB_3 + 32 * nt + pl];
         float best = -__builtin_inff();
+        [[maybe_unused]] unsigned long long kbest = 255ull;       // ARG: value +0 at point 0 of the wave
 #pragma unroll
         for (int q = 0; q < TP; ++q) {
             if (a.feat != nullptr) {       // optional (B,512,N) output: 4 consecutive points per 16-byte store
@@ -355,6 +184,18 @@ __global__ __launch_bounds__(e_waves(NS) * 64) void enc_kernel(EncArgs a) {
                     }
                 }
             }
+            if (ARG) {
+                // the feature's VALUE per point, as the plain kernel forms it for the maximum (relu(x + shift): fp32 addition
+                // is monotonic, so the largest of these is relu(max x + shift)); a missing point of a ragged tile never beats
+                // the initial key, and the tile's point 0 exists whenever any of its points does
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int pt = 32 * q + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const unsigned long long k = ((unsigned long long)f2u(relu(acc[q][r] + shift)) << 32) | (unsigned)(255 - pt);
+                    if (tile0[q] + pt - 32 * q < N && k > kbest) kbest = k;
+                }
+                continue;
+            }
             if (tile0[q] + TILE > N) {     // ragged or empty tile: its missing points do not take part in the max
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
@@ -365,11 +206,51 @@ __global__ __launch_bounds__(e_waves(NS) * 64) void enc_kernel(EncArgs a) {
             for (int r = 3; r < 15; r += 2) m = fmaxf(fmaxf(m, acc[q][r]), acc[q][r + 1]);
             best = fmaxf(best, fmaxf(m, acc[q][15]));
         }
+        if (ARG) {
+            const uint32_t klo = (uint32_t)kbest, khi = (uint32_t)(kbest >> 32);
+            const auto rl = __builtin_amdgcn_permlane32_swap(klo, klo, false, false);
+            const auto rh = __builtin_amdgcn_permlane32_swap(khi, khi, false, false);
+            const unsigned long long k0 = ((unsigned long long)rh[0] << 32) | rl[0], k1 = ((unsigned long long)rh[1] << 32) | rl[1];
+            const unsigned long long k = k0 > k1 ? k0 : k1;
+            if (!h) {
+                l_wmax[wave * EC4 + 32 * nt + pl] = u2f((uint32_t)(k >> 32));
+                l_widx[wave * EC4 + 32 * nt + pl] = (uint8_t)(255u - ((uint32_t)k & 255u));
+            }
+            continue;
+        }
         best = half_max(best);
         // max_p relu(x_p + shift) = relu(max_p x_p + shift): fp32 addition is monotonic; an all-empty wave gives 0
         if (!h) l_wmax[wave * EC4 + 32 * nt + pl] = fmaxf(best + shift, 0.f);
     }
     __syncthreads();
+    if (ARG) {
+        // ---- combine the waves (ascending points: a later wave wins only with a larger value; wave 0 of a workgroup is never
+        // empty), then the workgroups of the cloud
+        for (int f = threadIdx.x; f < EC4; f += EW * 64) {
+            uint32_t m = f2u(l_wmax[f]);
+            int w0 = 0;
+#pragma unroll
+            for (int w = 1; w < EW; ++w) {
+                const uint32_t v = f2u(l_wmax[w * EC4 + f]);
+                if (v > m) { m = v; w0 = w; }
+            }
+            const uint32_t point = (uint32_t)((blockIdx.x * EW + w0) * TP * TILE) + l_widx[w0 * EC4 + f];
+            __hip_atomic_fetch_max(a.keys + (size_t)bi * EC4 + f, ((unsigned long long)m << 32) | (0xFFFFFFFFu - point),
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // this workgroup's keys have left the CU
+        __syncthreads();
+        unsigned *tk = (unsigned *)l_wmax;
+        if (threadIdx.x == 0) *tk = __hip_atomic_fetch_add(a.ticket + bi, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        if (*tk != gridDim.x - 1) return;
+        for (int f = threadIdx.x; f < EC4; f += EW * 64) {
+            const unsigned long long k = __hip_atomic_load(a.keys + (size_t)bi * EC4 + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            a.gmax[(size_t)bi * EC4 + f] = u2f((uint32_t)(k >> 32));
+            a.arg[(size_t)bi * EC4 + f] = (int)(0xFFFFFFFFu - (uint32_t)k);
+        }
+        return;
+    }
     // ---- combine the waves, one integer atomicMax per feature (all values are >= 0, so the bit patterns order)
     for (int f = threadIdx.x; f < EC4; f += EW * 64) {
         float m = l_wmax[f];
@@ -379,17 +260,13 @@ __global__ __launch_bounds__(e_waves(NS) * 64) void enc_kernel(EncArgs a) {
     }
 }
 
-int e_ns_of(int precision) {
-    return precision == DPF_PREC_BF16 ? 1 : precision == DPF_PREC_BF16X3 ? 2 : precision == DPF_PREC_BF16X6 ? 3 : 0;
-}
-
-template <int NS>
+template <int NS, bool ARG>
 int launch_enc(const EncArgs &a, hipStream_t s) {
     constexpr int EW = e_waves(NS), EWG_POINTS = EW * e_tp(NS) * TILE;
-    const int lds = 8192 + 2 * ep_chunk_bytes(NS) + EW * EC4 * 4;
+    const int lds = 8192 + 2 * ep_chunk_bytes(NS) + EW * EC4 * (ARG ? 5 : 4);
     static LdsLimit limit;
-    if (hipError_t e = limit.ensure((const void *)enc_kernel<NS>, lds); e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(enc_kernel<NS>, dim3((a.N + EWG_POINTS - 1) / EWG_POINTS, a.B), dim3(EW * 64), lds, s, a);
+    if (hipError_t e = limit.ensure((const void *)enc_kernel<NS, ARG>, lds); e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL((enc_kernel<NS, ARG>), dim3((a.N + EWG_POINTS - 1) / EWG_POINTS, a.B), dim3(EW * 64), lds, s, a);
     return (int)hipGetLastError();
 }
 
@@ -422,6 +299,25 @@ extern "C" int dpf_encoder_forward(int B, int N, int precision, const void *pack
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = dpf_zero_async(gmax, sizeof(float) * (size_t)B * EC4, s);
     if (e != hipSuccess) return (int)e;
-    EncArgs a{(const uint8_t *)packed, x, gmax, feat, B, N};
-    return ns == 1 ? launch_enc<1>(a, s) : ns == 2 ? launch_enc<2>(a, s) : launch_enc<3>(a, s);
+    EncArgs a{(const uint8_t *)packed, x, gmax, feat, B, N, nullptr, nullptr, nullptr};
+    return ns == 1 ? launch_enc<1, false>(a, s) : ns == 2 ? launch_enc<2, false>(a, s) : launch_enc<3, false>(a, s);
+}
+
+// (B,512) 64-bit keys, then B tickets
+extern "C" size_t dpf_encoder_arg_scratch_bytes(int B) { return B > 0 ? (size_t)B * (EC4 * 8 + 4) : 0; }
+
+extern "C" int dpf_encoder_forward_arg(int B, int N, int precision, const void *packed, const float *x, float *gmax, int *arg,
+                                       void *scratch, dpf_stream_t stream) {
+    const int ns = e_ns_of(precision);
+    if (!ns || B < 0 || N <= 0) return DPF_EINVAL;
+    if (ns == 1) return DPF_ENOSUP;                          // bf16x3 and bf16x6 only
+    if (B == 0) return 0;
+    if (!packed || !x || !gmax || !arg || !scratch || ((uintptr_t)scratch & 7)) return DPF_EINVAL;
+    if (B > 65535) return DPF_ENOSUP;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = dpf_zero_async(scratch, dpf_encoder_arg_scratch_bytes(B), s);
+    if (e != hipSuccess) return (int)e;
+    EncArgs a{(const uint8_t *)packed, x, gmax, nullptr, B, N, arg, (unsigned long long *)scratch,
+              (unsigned *)((uint8_t *)scratch + (size_t)B * EC4 * 8)};
+    return ns == 2 ? launch_enc<2, true>(a, s) : launch_enc<3, true>(a, s);
 }

@@ -12,18 +12,24 @@ forward(input (B,3,N)) -> per-point features (B,512,N):
     statistics updated in place, argmax kept) and is an autograd node whose backward is the HIP backward pass to
     the twelve parameter gradients (and to the input when it requires grad).  Any other use of the features
     materialises them with tensor ops;
+  * eval mode with `eval_autograd = "hip"`, grad mode on and the input or any encoder parameter requiring grad: forward returns a
+    `FrozenPointFeatures`; its max over the points is one autograd node -- the fused launch with the argmax switched on, and
+    csrc/encoder_frozen.hip's backward with the running statistics frozen (networks/encoder_frozen_engine.py).  Any other use
+    of the features materialises them with tensor ops, which stay differentiable.  What the kernels do not serve (CPU tensors,
+    other dtypes or widths, precision "bf16") runs tensor ops with an EvalModeAutogradWarning;
   * eval mode with a differentiable input, other widths, BatchNorm without running statistics or with momentum=None: the
     tensor-op path (`self.features(input)`), on PyTorch-ROCm;
   * eval mode on CPU tensors raises (no CPU fallback).
 """
 import ctypes
+import warnings
 from collections import OrderedDict
 
 import torch
 import torch.nn as nn
 
 from .._lib import lib, check, current_stream, PREC
-from .layers import SharedDot, weight_state
+from .layers import SharedDot, weight_state, EvalModeAutogradWarning
 
 _HIP_ARCH = (3, 64, (128, 256, 512))
 
@@ -226,7 +232,50 @@ class TrainPointFeatures(PointFeatures):
         return self._full
 
 
+class FrozenPointFeatures(PointFeatures):
+    """Lazy (B,512,N) features of one EVAL-mode encoder call under autograd (eval_autograd = "hip"): the max over the points is the
+    frozen-statistics HIP autograd node; anything else materialises the features with tensor ops, which stay differentiable."""
+
+    def __init__(self, encoder, x):
+        super().__init__(encoder, x)
+        self.requires_grad = True
+
+    def max_over_points(self):
+        if self._max is None:
+            if self._full is not None:                                   # the features were asked for first
+                self._max = torch.max(self._full, dim=2)[0]
+            else:
+                from .encoder_frozen_engine import run_frozen_pool
+                self._max = run_frozen_pool(self._enc, self._x)
+        return self._max
+
+    def tensor(self):
+        if self._full is None:
+            self._full = self._enc.forward_torch(self._x)
+        return self._full
+
+    def amax(self, dim=None, keepdim=False):
+        return torch.amax(self, dim=dim, keepdim=keepdim)
+
+
+EVAL_AUTOGRAD = ("torch", "hip")
+
+
 class PointNetCloudEncoder(nn.Module):
+    # eval_autograd: "torch" (default) | "hip" = eval()-mode calls under autograd on the HIP kernels with frozen BatchNorm
+    # statistics (csrc/encoder_frozen.hip).  An attribute beside `precision`, not a parameter or buffer: not in the state dict.
+    _eval_autograd = "torch"
+
+    @property
+    def eval_autograd(self):
+        return self._eval_autograd
+
+    @eval_autograd.setter
+    def eval_autograd(self, value):
+        if value not in EVAL_AUTOGRAD:
+            raise ValueError("eval_autograd must be one of %s, got %r" % (list(EVAL_AUTOGRAD), value))
+        self.__dict__["_eval_autograd"] = value
+
     def __init__(self, init_n_channels, init_n_features, n_features):
         super().__init__()
         self.init_n_channels, self.init_n_features, self.n_features = init_n_channels, init_n_features, n_features
@@ -288,6 +337,15 @@ class PointNetCloudEncoder(nn.Module):
             and len({bn.momentum for bn in bns}) == 1 and all(getattr(self.features, n).weight.dtype == torch.float32 for n in _LAYERS)
 
     def forward(self, input):
+        if self.eval_autograd == "hip":
+            from .encoder_frozen_engine import wants_frozen_hip, frozen_hip_serves
+            if wants_frozen_hip(self, input):
+                if frozen_hip_serves(self, input):
+                    return FrozenPointFeatures(self, input.contiguous())
+                warnings.warn("eval_autograd='hip': this call (CPU tensors, a dtype other than float32, another architecture or "
+                              "precision 'bf16') is served by PyTorch tensor operations, not by the HIP kernels",
+                              EvalModeAutogradWarning, stacklevel=3)
+                return self.forward_torch(input)
         # other widths, or a differentiable input in eval mode: tensor ops
         if not self.hip_supported() or (torch.is_grad_enabled() and input.requires_grad and not self.training):
             return self.forward_torch(input)

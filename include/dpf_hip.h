@@ -449,6 +449,32 @@ int dpf_encoder_pack(int precision, const float *canon, void *packed, dpf_stream
 int dpf_encoder_forward(int B, int N, int precision, const void *packed, const float *x,
                         float *gmax, float *feat, dpf_stream_t stream);
 
+/* ---- PointNet cloud encoder, EVAL mode under autograd (frozen BatchNorm): forward with the argmax, and the backward ----
+ * dpf_encoder_forward_arg: dpf_encoder_forward (no feature output) that also yields arg (B,512) int32, the point that attains
+ *   each pooled value.  gmax is bit-identical to dpf_encoder_forward on the same inputs; arg[b,f] is the LOWEST point whose
+ *   layer-3 value equals the maximum; for a dead feature (gmax == 0) it is some point of the cloud.  One launch after the
+ *   zero fill of `scratch` (dpf_encoder_arg_scratch_bytes(B) bytes, 8-byte aligned, caller-owned): a 64-bit integer atomic
+ *   max per (cloud, feature) on (value bits << 32) | (0xFFFFFFFF - point), unpacked by the workgroup that arrives last at the
+ *   cloud's ticket -- order-independent, no floating-point atomics.  DPF_PREC_BF16X3 and DPF_PREC_BF16X6 (DPF_PREC_BF16:
+ *   DPF_ENOSUP); B <= 65535.
+ * dpf_encoder_frozen_backward: the backward of  pooled = max over the points of the eval-mode encoder  (running statistics;
+ *   what autograd derives from lib/networks/encoders.py:15-28 + models.py:106,124 under model.eval()).  canon: the block
+ *   `packed` was made from (dpf_encoder_pack, same precision); x, pooled, arg: the input and outputs of
+ *   dpf_encoder_forward_arg; g_pooled (B,512) = d loss / d pooled.  -> dcanon (optional; canon layout: dW, d gamma, d beta per
+ *   layer, the running-statistics slots are left untouched) and dx (optional; (B,3,N), fully written: zero away from the
+ *   argmax points); at least one of the two.  workspace: dpf_encoder_frozen_workspace_bytes(B) bytes, 16-byte aligned:
+ *   1.84 MB per cloud (59 MB at B = 32).  B <= 65535 is accepted as in the forward; in practice the workspace bounds B
+ *   (7.5 GB at B = 4096).
+ *   The work is B * 512 points whatever N is; 4 launches for dcanon, 6 with dx, whatever B and N are; no atomics, every sum in
+ *   an order fixed by the shapes (bit-reproducible).  The BatchNorm statistics are only read.  B = 1 and N = 1 are legal. */
+size_t dpf_encoder_arg_scratch_bytes(int B);
+int dpf_encoder_forward_arg(int B, int N, int precision, const void *packed, const float *x, float *gmax, int *arg,
+                            void *scratch, dpf_stream_t stream);
+size_t dpf_encoder_frozen_workspace_bytes(int B);
+int dpf_encoder_frozen_backward(int B, int N, int precision, const float *canon, const void *packed, const float *x,
+                                const float *pooled, const int *arg, const float *g_pooled, float *dcanon, float *dx,
+                                void *workspace, dpf_stream_t stream);
+
 /* ---- PointNet cloud encoder, TRAINING mode (batch-statistics BatchNorm) + max over the points, and backward ----
  * replaces, under model.train(), PointNetCloudEncoder.forward (lib/networks/encoders.py:27-28) followed by
  * torch.max(features, dim=2)[0] (lib/networks/models.py:131), and the gradients autograd derives for the
