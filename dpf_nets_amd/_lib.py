@@ -107,6 +107,9 @@ SIGNATURES = {
     "dpf_pointflow_nll_workspace_floats": (_sz, []),
     "dpf_pointflow_nll": (_i, [_i, _i, _i, _vp, _vp, _l, _l, _l, _vp, _l, _l, _l, _vp, _vp, _vp, _vp]),
     "dpf_pointflow_nll_backward": (_i, [_i, _i, _i, _vp, _vp, _l, _l, _l, _vp, _l, _l, _l, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dpf_occupancy_max_res": (_i, []),
+    "dpf_occupancy_grid_workspace_bytes": (_sz, [_i, _i, _i]),
+    "dpf_occupancy_grid": (_i, [_i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dpf_version": (ctypes.c_char_p, []),
 }
 

@@ -7,6 +7,10 @@
   knn (:125-154), lgan_mmd_cov (:157-169)           -- 1-NN accuracy, MMD and COV over those matrices (tensor arithmetic)
   compute_all_metrics (:172-200)                    -- the generation metrics (MMD / COV / 1-NNA, CD and EMD), its three matrix
                                                        pairs from networks.utils.pairwise_CD + pairwise_EMD
+  unit_cube_grid_point_cloud, jsd_between_point_cloud_sets, entropy_of_occupancy_grid, jensen_shannon_divergence, _jsdiv
+  (:206-321)                                        -- the occupancy-grid JSD; the nearest-centre binning of every point runs
+                                                       on the device (dpf_occupancy_grid, metrics/occupancy.py) instead of a
+                                                       scikit-learn tree query per cloud, the statistics stay host numpy / scipy
 
 Same signatures, return structures and values as the reference's loops.  What differs is how a row is fed: the reference
 expands sample i to (batch, n, 3) and copies it (`.contiguous()`) for every block of references; here the Chamfer launch
@@ -14,6 +18,9 @@ reads the one cloud through a zero batch stride (dpf_nndistance_strided_auto, sa
 in one more launch; the EMD entry point needs a dense batch, so only that operand is materialised.
 `accelerated_cd=False` asks the reference for its pure-PyTorch distChamfer (the O(N^2)-memory bmm form, :35-45); there
 is no CPU or tensor-op fallback in this package, so both values of the flag run the exact HIP Chamfer."""
+import warnings
+
+import numpy as np
 import torch
 
 from ..networks.utils import distChamferCUDA, emd_approx, chamfer_per_cloud, chamfer_cd_per_cloud  # noqa: F401
@@ -132,3 +139,94 @@ def compute_all_metrics(sample_pcs, ref_pcs, batch_size, accelerated_cd=False):
     for metric, (M_rr, M_rs, M_ss) in (("CD", (M_rr_cd, M_rs_cd, M_ss_cd)), ("EMD", (M_rr_emd, M_rs_emd, M_ss_emd))):
         results.update({"1-NN-%s-%s" % (metric, k): v for k, v in knn(M_rr, M_rs, M_ss, 1, sqrt=False).items() if 'acc' in k})
     return results
+
+
+#######################################################
+# JSD (:203-321; from https://github.com/optas/latent_3d_points)
+#######################################################
+def unit_cube_grid_point_cloud(resolution, clip_sphere=False):
+    """The centre coordinates of each cell of a 3D grid of resolution^3 cells placed in the unit cube (:206-224), float32, and
+    the spacing.  clip_sphere drops the cells whose centre lies outside the unit sphere (norm of the float32 centre > 0.5)."""
+    from .occupancy import unit_cube_grid
+    return unit_cube_grid(resolution, clip_sphere)
+
+
+def jsd_between_point_cloud_sets(sample_pcs, ref_pcs, resolution=28):
+    """The JSD between two sets of point clouds (:227-238) over the sphere-clipped grid: (S1, n1, 3) and (S2, n2, 3), numpy
+    arrays or CUDA float32 tensors."""
+    in_unit_sphere = True
+    sample_grid_var = entropy_of_occupancy_grid(sample_pcs, resolution, in_unit_sphere)[1]
+    ref_grid_var = entropy_of_occupancy_grid(ref_pcs, resolution, in_unit_sphere)[1]
+    return jensen_shannon_divergence(sample_grid_var, ref_grid_var)
+
+
+def entropy_of_occupancy_grid(pclouds, grid_resolution, in_sphere=False, verbose=False):
+    """The entropy of the occupancy-grid activation patterns of a collection of clouds (:241-280): every point counts for the
+    grid cell whose centre is nearest, a cell's Bernoulli variable is the share of the clouds that touch it.  Returns
+    (acc_entropy / n_cells, grid_counters): grid_counters float64 over the kept cells in unit_cube_grid_point_cloud's order.
+    pclouds: (S, n, 3) numpy array (uploaded to the current device as float32) or CUDA float32 tensor (read in place).  The
+    assignment is one launch (metrics/occupancy.py); a NaN or infinite point raises ValueError, as scikit-learn's query does."""
+    from scipy.stats import entropy
+    from .occupancy import nearest_grid_counts
+    if verbose:
+        epsilon = 10e-4
+        bound = 0.5 + epsilon
+        host = pclouds.detach().cpu().numpy() if isinstance(pclouds, torch.Tensor) else np.asarray(pclouds)
+        if abs(np.max(host)) > bound or abs(np.min(host)) > bound:
+            warnings.warn('Point-clouds are not in unit cube.')
+        if in_sphere and np.max(np.sqrt(np.sum(host ** 2, axis=2))) > bound:
+            warnings.warn('Point-clouds are not in unit sphere.')
+    counts, touching = nearest_grid_counts(pclouds, grid_resolution, in_sphere)
+    grid_counters = counts.astype(np.float64)
+    acc_entropy = 0.0
+    n = float(len(pclouds))
+    per_count = {}                                    # entropy([p, 1 - p]) once per distinct count; summed in the cells' order
+    for g in touching[touching > 0].tolist():
+        e = per_count.get(g)
+        if e is None:
+            p = float(g) / n
+            e = per_count[g] = entropy([p, 1.0 - p])
+        acc_entropy += e
+    return acc_entropy / len(grid_counters), grid_counters
+
+
+def jensen_shannon_divergence(P, Q):
+    if np.any(P < 0) or np.any(Q < 0):
+        raise ValueError('Negative values.')
+    if len(P) != len(Q):
+        raise ValueError('Non equal size.')
+    from scipy.stats import entropy
+
+    P_ = P / np.sum(P)  # Ensure probabilities.
+    Q_ = Q / np.sum(Q)
+
+    e1 = entropy(P_, base=2)
+    e2 = entropy(Q_, base=2)
+    e_sum = entropy((P_ + Q_) / 2.0, base=2)
+    res = e_sum - ((e1 + e2) / 2.0)
+
+    res2 = _jsdiv(P_, Q_)
+
+    if not np.allclose(res, res2, atol=10e-5, rtol=0):
+        warnings.warn('Numerical values of two JSD methods don\'t agree.')
+
+    return res
+
+
+def _jsdiv(P, Q):
+    """another way of computing JSD"""
+
+    def _kldiv(A, B):
+        a = A.copy()
+        b = B.copy()
+        idx = np.logical_and(a > 0, b > 0)
+        a = a[idx]
+        b = b[idx]
+        return np.sum([v for v in a * np.log2(a / b)])
+
+    P_ = P / np.sum(P)
+    Q_ = Q / np.sum(Q)
+
+    M = 0.5 * (P_ + Q_)
+
+    return 0.5 * (_kldiv(P_, M) + _kldiv(Q_, M))

@@ -229,7 +229,7 @@ def pairwise_EMD(clouds1, clouds2, bs=512, shard_rows=False):
 # The consumers of pairwise_CD in the reference's generative evaluation (evaluating.py:245-262): coverage, minimum matching
 # distance and the 1-NN two-sample accuracy over the (N1, N2) Chamfer matrices, the voxel-occupancy Jensen-Shannon divergence
 # over the clouds themselves, and the running-average helper of both loops.  Same names, arguments and values as
-# lib/networks/utils.py:8-22, 45-87, 120-146; tensor / numpy plumbing, no kernels.
+# lib/networks/utils.py:8-22, 45-87, 120-146; tensor / numpy plumbing -- the one kernel is the voxel binning of CUDA clouds.
 # ----------------------------------------------------------------------------------------------------------------
 class AverageMeter:
     """lib/networks/utils.py:8-22: last value, running sum / count / mean."""
@@ -278,8 +278,20 @@ def get_voxel_occ_dist(all_clouds, clouds_flag='gen', res=28, bound=0.5, bs=128,
     """Occupancy distribution of the points of all clouds over the res^3 voxels of [-0.5, 0.5)^3 (utils.py:45-80).
     all_clouds: (K, n, 3) numpy array.  A point outside the cube (or NaN) is not counted.  The bin edges are the reference's
     doubles -0.5 + i / res and the intervals half-open on the right, so every point lands in the voxel the reference
-    picks; the counting is one bincount instead of batched comparison tables (`bs` is accepted and ignored)."""
+    picks; the counting is one bincount instead of batched comparison tables (`bs` is accepted and ignored).
+    A CUDA float32 tensor (what evaluating.py:249 holds before its `.cpu().numpy()`) is binned where it is: one launch
+    against the same table of edges (metrics/occupancy.py, dpf_occupancy_grid mode 0), and only the res^3 counts and the two
+    diagnostics' flags come back.  Same return value, same two printed lines."""
     import numpy as np
+    if isinstance(all_clouds, torch.Tensor) and all_clouds.is_cuda:
+        from ..metrics.occupancy import cube_grid_counts
+        counts, n_nans, out_of_bounds = cube_grid_counts(all_clouds, res, warn_bound=bound)
+        if out_of_bounds and warning:
+            print('{} clouds out of cube bounds: [-{}; {}]'.format(clouds_flag, bound, bound))
+        if n_nans > 0:
+            print('{} NaN values in point cloud tensors.'.format(n_nans))
+        counts = counts.astype(np.uint64).reshape(res, res, res)
+        return counts.astype(np.float64) / counts.sum()
     all_clouds = np.asarray(all_clouds)
     if np.any(np.fabs(all_clouds) > bound) and warning:
         print('{} clouds out of cube bounds: [-{}; {}]'.format(clouds_flag, bound, bound))

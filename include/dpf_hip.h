@@ -675,6 +675,29 @@ int dpf_film_frozen_backward(int K, int B, int G, const float *g, const float *W
                              float *dgamma, float *dbeta, float *dW1, float *db1, float *dg, float *workspace,
                              unsigned *ticket, int accumulate, dpf_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * Occupancy grids of the two Jensen-Shannon metrics (csrc/occupancy.hip): every point of the (S, n, 3) point-major fp32
+ * clouds is put into one cell of a res^3 grid; counts[cell] = points, clouds_touching[cell] = clouds with at least one
+ * point there.  Integer atomics: exact and independent of order.  All three outputs are zeroed by the call.
+ *   mode 0, cube bins (lib/networks/utils.py:45-80): the voxel of a coordinate x is the i with edges[i] <= x < edges[i+1],
+ *     compared in double against the caller's table of res + 1 edges; cell = (ix * res + iy) * res + iz.  A point with a
+ *     coordinate outside every interval, or NaN, is not counted.  centres / kept / kept_xyz are unused (kept must be NULL).
+ *   mode 1, nearest centre (lib/metrics/evaluation_metrics.py:241-280): cell = the argmin over the K kept centres of
+ *     (dx*dx + dy*dy) + dz*dz in double (the fp32 inputs widened), the lowest kept index on an exact tie.  centres: the res
+ *     per-axis centre values, increasing; kept: (res^3) full-grid cell -> kept index or -1, increasing over the kept cells,
+ *     or NULL for the full grid (then K = res^3); kept_xyz: (K, 3) the kept centres, each coordinate one of `centres`.
+ *     A point with a NaN or infinite coordinate is not counted.
+ * flags: 4 words -- [0] points with a non-finite coordinate, [1] NaN coordinates, [2] nonzero if some |coordinate| >
+ * warn_bound, [3] unused.  res <= the value the max_res query returns (the per-cloud presence bitmap lives in LDS), else
+ * DPF_ENOSUP.  workspace: the workspace_bytes query's size (nonzero only for clouds long enough to be split over several
+ * workgroups); S and n are unbounded, the call chunks its launches. */
+int dpf_occupancy_max_res(void);
+size_t dpf_occupancy_grid_workspace_bytes(int S, int n, int res);
+int dpf_occupancy_grid(int S, int n, const float *clouds, int res, int mode, const double *edges, const float *centres,
+                       const int *kept, const float *kept_xyz, int K, float warn_bound, unsigned long long *counts,
+                       unsigned int *clouds_touching, unsigned int *flags, void *workspace, size_t workspace_bytes,
+                       dpf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
