@@ -28,12 +28,16 @@ def projection_loss(lists, seed):
 _CACHE = {}
 
 
-def oracle64(seed, n_flows, nf, G, B, mode):
+def oracle64(seed, n_flows, nf, G, B, mode, mutate=None):
     """-> dict: gs, mus, lvs (S,B,G), dg (B,G) and grads {reference parameter name: gradient}, all float64 numpy.  Computed once
-    per case and shared; callers must not write into it."""
-    key = (seed, n_flows, nf, G, B, mode)
+    per case and shared; callers must not write into it.  mutate(state, seed) (tests/gprior_train_ref.py) is applied to a copy of
+    the seeded state first."""
+    key = (seed, n_flows, nf, G, B, mode) + (() if mutate is None else (mutate.__name__,))
     if key not in _CACHE:
-        st = {k: (v.double() if v.dtype == torch.float32 else v) for k, v in FO.to_torch(GO.make_gprior_state(seed, n_flows, nf, G)).items()}
+        state = GO.make_gprior_state(seed, n_flows, nf, G)
+        if mutate is not None:
+            state = mutate({k: np.array(v, copy=True) for k, v in state.items()}, seed)
+        st = {k: (v.double() if v.dtype == torch.float32 else v) for k, v in FO.to_torch(state).items()}
         params = {k: v.requires_grad_(True) for k, v in st.items()
                   if v.dtype == torch.float64 and "running" not in k and not k.endswith("eps")}
         g = torch.from_numpy(GO.gprior_inputs(seed, B, G)).double().requires_grad_(True)

@@ -6,6 +6,7 @@ path's f16x3 bar (GRAD_REL["f16x3"] = 2e-4 of test_gpu_flow_train.py), parameter
 max(2e-4, R32_FACTOR["f16x3"] x the fp32 tensor-op path's own error against float64 on the same inputs) with bias_floor;
 grad_p through close_but_kinks (a ReLU flip is local to one point: at most max(3, 2e-4 size) elements outside, median <= tol / 10)."""
 import json
+import math
 import os
 import warnings
 
@@ -16,6 +17,7 @@ import torch
 from oracle import flow_oracle as FO
 from oracle import golden_io
 from oracle.gen_golden import layer_inputs, _grad_projection
+from tests import flow_hostile as H
 from tests.gradcheck import check_projections
 from tests.test_gpu_flow import REL
 from tests.test_gpu_flow_train import GRAD_REL, R32_FACTOR, rel, bias_floor, close_but_kinks
@@ -104,13 +106,15 @@ def _loss(nets, ps, mus, lvs, tp, mode):
 _RUNS = {}
 
 
-def _run(nets, n_flows, G, B, N, mode, impl, flat=False, seed=5):
-    """One forward + backward of the decoder: impl "hip" (eval_autograd), "torch" (fp32 tensor ops), "torch64".  Cached."""
-    key = (n_flows, G, B, N, mode, impl, flat)
+def _run(nets, n_flows, G, B, N, mode, impl, flat=False, seed=5, mutate=None, variant=None):
+    """One forward + backward of the decoder: impl "hip" (eval_autograd), "torch" (fp32 tensor ops), "torch64".  Cached.
+    mutate(state, seed) (tests/flow_hostile.py) is applied to the seeded state, variant names one of its input clouds."""
+    key = (n_flows, G, B, N, mode, impl, flat, seed, getattr(mutate, "__name__", None), variant)
     if key in _RUNS:
         return _RUNS[key]
-    sd = FO.to_torch(FO.make_decoder_state(seed, n_flows, 64, G))
-    tgt, z, g = FO.synthetic_inputs(seed, B, N, G)
+    state = FO.make_decoder_state(seed, n_flows, 64, G)
+    sd = FO.to_torch(state if mutate is None else mutate(state, seed))
+    tgt, z, g = FO.synthetic_inputs(seed, B, N, G) if variant is None else H.hostile_inputs(seed, B, N, G, variant)
     dec = nets.LocalCondRNVPDecoder(n_flows, 64, G, weight_std=0.01)
     dec.load_state_dict(sd, strict=True)
     dec = dec.cuda().eval()
@@ -132,6 +136,7 @@ def _run(nets, n_flows, G, B, N, mode, impl, flat=False, seed=5):
     _loss(nets, list(ps), list(mus), list(lvs), tp, mode).backward()
     res = dict(ps=[x.detach() for x in ps], mus=[x.detach() for x in mus], lvs=[x.detach() for x in lvs], gp=tp.grad, gg=tg.grad,
                grads={k: (None if v.grad is None else v.grad.clone()) for k, v in dec.named_parameters()}, store=store,
+               precision=dec.stack().last_precision if impl == "hip" else None,
                grad_storage={k: v.grad.untyped_storage().data_ptr() for k, v in dec.named_parameters() if v.grad is not None})
     _RUNS[key] = res
     return res
@@ -173,11 +178,65 @@ def test_stack_vs_float64_tensor_ops(n_flows, G, B, N, mode):
     _compare(h, t, t32, (n_flows, G, B, N, mode))
 
 
+@pytest.mark.parametrize("variant", H.VARIANTS)
+@pytest.mark.parametrize("n_flows,G,B,N,mode", [(2, 128, 1, 40, "inverse"), (2, 128, 3, 100, "direct"), (2, 128, 33, 64, "direct"),
+                                                (2, 512, 3, 100, "direct")])
+def test_stack_vs_float64_tensor_ops_hostile(n_flows, G, B, N, mode, variant):
+    """Test 3 on the states and clouds of tests/flow_hostile.py (gamma0 negative, zero and at the f16x3 guard, running variances
+    over four decades, FiLM factors from 7e-7 to several hundred, dead / constant units, a saturated and an identity layer), through
+    _compare with its bars unchanged; f16x3 is what was served.  On top, against float64 autograd: the zero-gamma0 feature's
+    d gamma0 = sum dh0 xhat is live and its d W0 row exactly 0; the dead unit's dW1 column, d beta0 and d gamma0 are exactly 0; the
+    identity layer's d sd2.weight and d sd2.bias are live and at GRAD.
+
+    Measured over the twelve cases, against float64: outputs at most 1.3e-6 (OUT = 4e-6); the worst parameter gradient 6.6e-5 (GRAD =
+    2e-4; a FiLM w-net's second weight at (B 1, N 40, inverse), where the fp32 tensor-op path is at 3.1e-7 of float64); the identity
+    layer's d sd2 at most 2.2e-6."""
+    nets = _gpu()
+    h, t, t32 = (_run(nets, n_flows, G, B, N, mode, impl, seed=H.SEED, mutate=H.hostile_flow, variant=variant)
+                 for impl in ("hip", "torch64", "torch"))
+    _compare(h, t, t32, (n_flows, G, B, N, mode, "hostile", variant))
+    assert h["precision"] == "f16x3"
+    prefixes = H.layer_prefixes(t["grads"])
+    assert len(prefixes) == 3 * n_flows
+    G64, Gh = t["grads"], h["grads"]
+    live_zero = 0
+    for pre in prefixes:
+        for br in FO.BRANCHES:
+            t0 = "%sT_%s_0.%s_" % (pre, br, br)
+            w0, g0, b0, w1 = t0 + "sd0.weight", t0 + "sd0_bn.weight", t0 + "sd0_bn.bias", t0 + "sd1.weight"
+            if G64[g0] is None:                            # a net the loss does not reach (direct mode: the last layer's mu net)
+                continue
+            r, _ = H.roles(H.SEED, pre, br)
+            z, d = r["zero"], r["dead"]
+            # the project's measure: the entry's error over the TENSOR's scale.  That holds the entry itself to GRAD * scale / |ref|:
+            # it is counted as checked only where it is at least 1e-2 of the scale (the entry then within 2 % of itself; a kernel
+            # that divided by gamma0 or dropped the term is far outside).  In the identity layer's nets no gradient reaches the
+            # conditioner: d gamma0 is an all-zero tensor there and the comparison is 0 against 0.
+            got, ref, scale = float(Gh[g0][z]), float(G64[g0][z]), float(G64[g0].abs().max())
+            assert math.isfinite(got) and abs(got - ref) <= GRAD * scale, (g0, "gamma0 = 0", got, ref, scale)
+            if scale == 0.0:
+                assert pre == prefixes[H.ID_LAYER] and got == 0.0, g0
+            elif abs(ref) >= 1e-2 * scale:
+                assert got != 0.0 and abs(got - ref) <= 100 * GRAD * abs(ref), (g0, got, ref)
+                live_zero += 1
+            assert float(G64[w0][0, z].abs().max()) == 0.0 and float(Gh[w0][0, z].abs().max()) == 0.0, (w0, "row of gamma0 = 0")
+            for k, a64, a in ((w1, G64[w1][0, :, d], Gh[w1][0, :, d]), (b0, G64[b0][d], Gh[b0][d]), (g0, G64[g0][d], Gh[g0][d])):
+                assert float(a64.abs().max()) == 0.0 and float(a.abs().max()) == 0.0, (k, "dead unit")
+    assert live_zero >= 4, live_zero                        # d gamma0 = sum dh0 xhat does not involve gamma0 (float64: 7 to 10 of the 9 to 10 reached nets)
+    for br in FO.BRANCHES:
+        for leaf in ("weight", "bias"):
+            k = "%sT_%s_1.%s_sd2.%s" % (prefixes[H.ID_LAYER], br, br, leaf)
+            assert G64[k] is not None and float(G64[k].abs().max()) > 0.0, k
+            r_ = rel(Gh[k], G64[k], bias_floor(G64, k))
+            print("GRADREL identity layer", k, r_)
+            assert r_ <= GRAD, (k, r_)
+
+
 def test_repeated_calls_are_bit_identical():
     """4"""
     nets = _gpu()
     a = _run(nets, 2, 128, 3, 1000, "direct", "hip")
-    _RUNS.pop((2, 128, 3, 1000, "direct", "hip", False))
+    _RUNS.pop((2, 128, 3, 1000, "direct", "hip", False, 5, None, None))
     b = _run(nets, 2, 128, 3, 1000, "direct", "hip")
     assert torch.equal(a["gp"], b["gp"]) and torch.equal(a["gg"], b["gg"])
     for k in a["grads"]:

@@ -206,6 +206,25 @@ def test_training_hip_vs_tensor_op_path(B, N, mode, prec):
     _hip_vs_tensor_ops(nets, B, N, mode, prec, 31)
 
 
+@pytest.mark.parametrize("B,N,mode", [(8, 2048, "direct"), (3, 1000, "inverse")])
+def test_training_hip_vs_tensor_op_path_hostile(B, N, mode):
+    """The test above at the default precision on the parameter part of tests/flow_hostile.py (running statistics are not read in
+    training mode): gamma0 negative and exactly zero, a dead and a constant unit (batch variance exactly 0: the reference's
+    BatchNorm output is exactly beta0), a zero sd1 row (h1 == 0, batch variance 0), FiLM factors from 7e-7 to several hundred with cb
+    at +-3, a saturated and an identity layer -- every floor and factor of _hip_vs_tensor_ops unchanged, the running statistics
+    after the step against float64 at rtol 1e-4, atol 1e-5 included.
+
+    The cases are well-posed: with the fp32 tensor-op path in the HIP stack's place both pass every floor (its worst parameter
+    gradient 3.7e-4 of float64, a BN0 bias at (8, 2048, direct)).  (3, 1000, inverse) passes: worst parameter gradient 1.2e-4 of
+    float64 (the fp32 tensor-op path on that gradient: 6.1e-6).  (8, 2048, direct) has been seen to FAIL on one figure, and the
+    floor is left where it is: d loss / d g at 9.87e-4 of float64 against GG_REL = KINK_CLOUD / N = 9.77e-4, the size of two
+    flipped ReLUs in one cloud where the floor allows for one; the cause has not been taken apart."""
+    nets = _gpu()
+    from dpf_nets_amd.networks import train_engine
+    from tests.flow_hostile import hostile_flow_train
+    _hip_vs_tensor_ops(nets, B, N, mode, train_engine.TRAIN_PRECISION, 31, mutate=hostile_flow_train)
+
+
 def test_training_gradient_errors_over_seeds_are_the_fp32_tensor_ops_own(monkeypatch):
     """the ReLU-flip floors of the test above (KINK_SUM / P, KINK_CLOUD / N, bias_floor) were re-derived in r05 from what ONE
     seed drew.  What they stand for is a mechanism, and this test holds the mechanism instead of a constant: training-mode BatchNorm
@@ -251,7 +270,7 @@ def test_training_gradient_errors_over_seeds_are_the_fp32_tensor_ops_own(monkeyp
     assert np.median(a[:, 2]) <= 2.0 * np.median(a[:, 3]) + 8.0, a[:, 2:]
 
 
-def _hip_vs_tensor_ops(nets, B, N, mode, prec, seed):
+def _hip_vs_tensor_ops(nets, B, N, mode, prec, seed, mutate=None):
     kf, loose = (5e-4, 1.0) if prec in ("bf16x6", "f16x3") else (1e-2, 10.0)
     STACK_OUT_REL, STACK_GRAD_REL = STACK_TOL[prec]
     # (r05, ADVICE r04: the floors are capped -- at (2, 40) they had grown to 5e-2 / 0.4 and checked nothing; what the tiny and
@@ -260,7 +279,8 @@ def _hip_vs_tensor_ops(nets, B, N, mode, prec, seed):
     STACK_GRAD_REL = max(STACK_GRAD_REL, min(KINK / (B * N), KINK_CAP))
     PARAM_REL = max(2 * loose * STACK_TOL[prec][1], min(KINK_SUM / (B * N), KINK_SUM_CAP))
     n_flows, G = 2, 128
-    sd = FO.to_torch(FO.make_decoder_state(seed, n_flows, 64, G))
+    state = FO.make_decoder_state(seed, n_flows, 64, G)
+    sd = FO.to_torch(state if mutate is None else mutate(state, seed))
     tgt, z, g = FO.synthetic_inputs(seed, B, N, G)
     src = tgt if mode == "inverse" else z
     res = {}

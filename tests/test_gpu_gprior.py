@@ -19,6 +19,7 @@ import torch
 
 from oracle import flow_oracle as FO
 from oracle import gprior_oracle as GO
+from tests.gprior_train_ref import hostile_bn, make_state
 
 pytestmark = pytest.mark.gpu
 
@@ -92,9 +93,9 @@ def test_c_abi_vs_reference_golden(golden_dir):
     assert L.dpf_gprior_forward(2, 0, 8, 8, 0, codes, packed.data_ptr(), None, None, None, None, None, None, 1e-6, None) == 0
 
 
-def _decoder(nets, seed, n_flows, nf, G):
+def _decoder(nets, seed, n_flows, nf, G, mutate=None):
     dec = nets.GlobalRNVPDecoder(n_flows, nf, G)
-    dec.load_state_dict(FO.to_torch(GO.make_gprior_state(seed, n_flows, nf, G)), strict=True)
+    dec.load_state_dict(FO.to_torch(make_state(seed, n_flows, nf, G, mutate)), strict=True)
     return dec.cuda().eval()
 
 
@@ -102,12 +103,23 @@ def _decoder(nets, seed, n_flows, nf, G):
 def test_module_vs_oracle_and_round_trip(n_flows, nf, G, B):
     """GlobalRNVPDecoder.forward in eval mode is the HIP launch (FlowList views of its buffers); against the oracle
     on the same seeded weights and inputs, and the tensor-op path on the GPU; direct then inverse returns the input."""
+    _module_vs_oracle_and_round_trip(n_flows, nf, G, B, None)
+
+
+@pytest.mark.parametrize("n_flows,nf,G,B", [(3, 40, 24, 301), (1, 8, 2, 3)])
+def test_module_vs_oracle_and_round_trip_hostile(n_flows, nf, G, B):
+    """The two smallest shapes above under tests/gprior_train_ref.hostile_bn: negative and exactly zero mlp0_bn.weight entries and a
+    dead hidden unit in every net (the eval kernel folds gamma / sqrt(running_var + eps) into one per-feature scale)."""
+    _module_vs_oracle_and_round_trip(n_flows, nf, G, B, hostile_bn)
+
+
+def _module_vs_oracle_and_round_trip(n_flows, nf, G, B, mutate):
     nets = _gpu()
     seed = 300 + G + B
-    dec = _decoder(nets, seed, n_flows, nf, G)
+    dec = _decoder(nets, seed, n_flows, nf, G, mutate)
     g = GO.gprior_inputs(seed, B, G)
     tg = torch.from_numpy(g).cuda()
-    st = FO.to_torch(GO.make_gprior_state(seed, n_flows, nf, G))
+    st = FO.to_torch(make_state(seed, n_flows, nf, G, mutate))
     from dpf_nets_amd.networks.flowlist import FlowList
     from dpf_nets_amd.networks.losses import total_logvar
     for mode in ("direct", "inverse"):

@@ -23,6 +23,7 @@ import torch
 from oracle import flow_oracle as FO
 from oracle import gprior_oracle as GO
 from tests.gprior_frozen_ref import NAMES, oracle64, projection_loss, projection_weights, rel
+from tests.gprior_train_ref import hostile_bn, make_state
 
 pytestmark = pytest.mark.gpu
 
@@ -47,9 +48,9 @@ def _warned(caught):
     assert any(issubclass(w.category, EvalModeAutogradWarning) for w in caught)
 
 
-def _decoder(nets, seed, n_flows, nf, G, impl="hip"):
+def _decoder(nets, seed, n_flows, nf, G, impl="hip", mutate=None):
     dec = nets.GlobalRNVPDecoder(n_flows, nf, G)
-    dec.load_state_dict(FO.to_torch(GO.make_gprior_state(seed, n_flows, nf, G)), strict=True)
+    dec.load_state_dict(FO.to_torch(make_state(seed, n_flows, nf, G, mutate)), strict=True)
     dec = dec.cuda().eval()
     dec.eval_autograd = impl
     return dec
@@ -71,13 +72,13 @@ def _seed(G, B):
 _RUNS = {}
 
 
-def _run(nets, n_flows, nf, G, B, mode, fresh=False):
+def _run(nets, n_flows, nf, G, B, mode, fresh=False, mutate=None):
     """Forward + backward of the seeded projection loss through the HIP node with g requiring grad.  Cached unless fresh."""
-    key = (n_flows, nf, G, B, mode)
+    key = (n_flows, nf, G, B, mode) + (() if mutate is None else (mutate.__name__,))
     if not fresh and key in _RUNS:
         return _RUNS[key]
     seed = _seed(G, B)
-    dec = _decoder(nets, seed, n_flows, nf, G)
+    dec = _decoder(nets, seed, n_flows, nf, G, mutate=mutate)
     g = torch.from_numpy(GO.gprior_inputs(seed, B, G)).cuda().requires_grad_(True)
     lists = _call(dec, g, mode)
     projection_loss(lists, seed).backward()
@@ -122,6 +123,28 @@ def test_stack_vs_float64_oracle(n_flows, nf, G, B, mode):
     for got, p in zip(run["outs"], plain):
         assert torch.equal(got, p.stacked)                          # the forward IS the fused eval launch
     _check_vs_oracle(run["outs"], run["dg"], run["grads"], oracle64(_seed(G, B), n_flows, nf, G, B, mode), (n_flows, nf, G, B, mode))
+
+
+@pytest.mark.parametrize("mode", ["direct", "inverse"])
+@pytest.mark.parametrize("n_flows,nf,G,B", [(1, 8, 2, 3), (2, 16, 8, 5)])
+def test_stack_vs_float64_oracle_hostile(n_flows, nf, G, B, mode):
+    """The two smallest cases above under tests/gprior_train_ref.hostile_bn -- negative and exactly zero mlp0_bn.weight entries and a
+    dead hidden unit in every net -- at the same bars: the closed-form d gamma, d W0 and d beta of csrc/gprior_frozen.hip hold for
+    gamma <= 0 only if their signs do.  The zero-gamma unit's d gamma is live and its d W0 row exactly 0."""
+    nets = _gpu()
+    run = _run(nets, n_flows, nf, G, B, mode, mutate=hostile_bn)
+    with torch.no_grad():
+        plain = run["dec"](run["g"], mode=mode)
+    for got, p in zip(run["outs"], plain):
+        assert torch.equal(got, p.stacked)
+    ref = oracle64(_seed(G, B), n_flows, nf, G, B, mode, mutate=hostile_bn)
+    _check_vs_oracle(run["outs"], run["dg"], run["grads"], ref, (n_flows, nf, G, B, mode, "hostile"))
+    for k, v in run["grads"].items():
+        r = ref["grads"][k]
+        if k.endswith("mlp0_bn.weight"):
+            assert float(run["dec"].state_dict()[k][0]) == 0.0 and r[0] != 0.0 and float(v[0]) != 0.0, (k, r[0], float(v[0]))
+        elif k.endswith("mlp0.weight"):
+            assert not r[0].any() and not v[0].any(), k                    # gamma = 0: the d W0 row is exactly 0
 
 
 @pytest.mark.parametrize("n_flows,nf,G,B,mode", [(3, 40, 24, 301, "inverse"), (2, 16, 8, 5, "direct")])
