@@ -11,24 +11,20 @@
 #include <stdint.h>
 
 #include "dpf_hip.h"
+#include "gprior_common.h"
 
 namespace {
 
 constexpr int THREADS = 1024;      // the steps are chains of dependent round trips: many short dot products, not few long ones
 constexpr int PACK_THREADS = 256;
-constexpr int MAX_STEPS = 256;
 
-// step code (2 bits): which coordinates a step warps, RealNVPFlowCouple's two patterns (flows.py:224-233)
-//   0: even (keep odd)   1: odd (keep even)   2: first half (keep second)   3: second half (keep first)
-__host__ __device__ inline size_t canon_net_floats(int K, int nf) { return (size_t)2 * nf * K + 4 * (size_t)nf + K; }
-__host__ __device__ inline size_t packed_net_floats(int K, int nf) { return (size_t)2 * nf * K + 2 * (size_t)nf + K; }
-
-// canon (per step, per net: mu then logvar; the reference's state_dict order, flows.py:176-196):
-//   W0 [nf][K] | bn.weight | bn.bias | bn.running_mean | bn.running_var | W1 [K][nf] | b1 [K]
+// canon (per step, per net): gprior_common.h, with the running-statistics slots: net_floats(K, nf, 4)
 // packed (per step, per net):  W0t [K][nf] | a [nf] | c [nf] | W1t [nf][K] | b1 [K]      a = gamma / sqrt(var + eps), c = beta - mean a
+// (= net_floats(K, nf, 2); spelled out: through that call the kernels' address arithmetic compiles to other instructions)
+__host__ __device__ inline size_t packed_net_floats(int K, int nf) { return (size_t)2 * nf * K + 2 * (size_t)nf + K; }
 __global__ __launch_bounds__(PACK_THREADS) void gprior_pack_kernel(int nets, int K, int nf, float bn_eps, const float *__restrict__ canon,
                                                               float *__restrict__ packed) {
-    const size_t cn = canon_net_floats(K, nf), pn = packed_net_floats(K, nf);
+    const size_t cn = net_floats(K, nf, 4), pn = packed_net_floats(K, nf);
     const size_t total = (size_t)nets * pn;
     for (size_t e = (size_t)blockIdx.x * PACK_THREADS + threadIdx.x; e < total; e += (size_t)gridDim.x * PACK_THREADS) {
         const size_t net = e / pn;
@@ -59,7 +55,7 @@ struct GArgs {
     float eps;
     const float *packed, *g;
     float *gs, *mus, *lvs, *sum_lv, *g_out;
-    uint32_t codes[MAX_STEPS / 16];
+    StepCodes codes;
 };
 
 // Workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every outstanding global store to be
@@ -135,9 +131,7 @@ __global__ __launch_bounds__(THREADS) void gprior_kernel(GArgs a) {
     const size_t pn = packed_net_floats(K, nf);
     for (int t = 0; t < a.S; ++t) {
         const int s = a.inverse ? a.S - 1 - t : t;
-        const int code = (a.codes[s >> 4] >> ((s & 15) * 2)) & 3;
-        // kept coordinate k of the step sits at kmul * k + kadd, warped coordinate i at kmul * i + wadd
-        const int kmul = code < 2 ? 2 : 1, kadd = code == 0 ? 1 : code == 2 ? K : 0, wadd = code == 1 ? 1 : code == 3 ? K : 0;
+        const auto [kmul, kadd, wadd] = step_index(step_code(a.codes, s), K);
         const float *pk = a.packed + (size_t)s * 2 * pn;
         // the step's BatchNorm vectors and biases are fetched now, with the first-map weights, not when they are needed:
         // a step is a chain of dependent round trips to L2 / the infinity cache, and these two would be links of it
@@ -206,7 +200,7 @@ __global__ __launch_bounds__(THREADS) void gprior_kernel(GArgs a) {
 
 extern "C" {
 
-size_t dpf_gprior_canon_floats(int G, int n_features) { return G > 0 && n_features > 0 ? 2 * canon_net_floats(G / 2, n_features) : 0; }
+size_t dpf_gprior_canon_floats(int G, int n_features) { return G > 0 && n_features > 0 ? 2 * net_floats(G / 2, n_features, 4) : 0; }
 
 size_t dpf_gprior_packed_floats(int n_steps, int G, int n_features) {
     return n_steps > 0 && G > 0 && n_features > 0 ? (size_t)n_steps * 2 * packed_net_floats(G / 2, n_features) : 0;
@@ -230,10 +224,7 @@ int dpf_gprior_forward(int n_steps, int B, int G, int n_features, int mode, cons
     GArgs a = {};
     a.S = n_steps; a.B = B; a.G = G; a.nf = n_features; a.inverse = mode; a.eps = eps;
     a.packed = packed; a.g = g; a.gs = gs; a.mus = mus; a.lvs = lvs; a.sum_lv = sum_lv; a.g_out = g_out;
-    for (int s = 0; s < n_steps; ++s) {
-        if (codes[s] < 0 || codes[s] > 3) return DPF_EINVAL;
-        a.codes[s >> 4] |= (uint32_t)codes[s] << ((s & 15) * 2);
-    }
+    if (!pack_step_codes(n_steps, codes, a.codes)) return DPF_EINVAL;
     // rows per workgroup: 1 up to one workgroup per CU, 2 beyond (the weights are read once per workgroup and step);
     // the hidden range of the second map is split over the threads the (net, i) items leave idle
     const int rb = B > 256 ? 2 : 1;

@@ -17,17 +17,13 @@
 #include <stdint.h>
 
 #include "dpf_hip.h"
+#include "gprior_common.h"
 
 namespace {
 
 constexpr int THREADS = 1024, WAVES = THREADS / 64;
 constexpr int PT = 256;
-constexpr int MAX_STEPS = 256;
 constexpr int MAX_ROW_BLOCKS = 1024;
-
-// floats of one net in the canonical block: W0 | gamma | beta | [running_mean | running_var] | W1 | b1  (nbn = 4 with the
-// running-statistics slots of dpf_gprior_pack's layout, 2 in the parameters-only layout)
-__host__ __device__ inline size_t net_floats(int K, int nf, int nbn) { return (size_t)2 * nf * K + (size_t)nbn * nf + K; }
 
 struct FArgs {
     int S, B, G, nf, inverse, nbn, parts2, parts3;
@@ -35,10 +31,8 @@ struct FArgs {
     const float *canon, *stats, *g, *gs, *mus, *lvs, *d_gs, *d_mus, *d_lvs;
     float *dg, *dcanon;
     float *w_sw, *w_xh, *w_dy, *w_do;          // workspace: (S,B,2nf) Swish outputs, xhat, dy; (S,B,2K) d_o
-    uint32_t codes[MAX_STEPS / 16];
+    StepCodes codes;
 };
-
-__device__ __forceinline__ int step_code(const FArgs &a, int s) { return (a.codes[s >> 4] >> ((s & 15) * 2)) & 3; }
 
 // running_mean [nf] | running_var [nf] of net n = 2 * step + (0 mu, 1 logvar): inside the canonical block, or the separate block
 __device__ __forceinline__ const float *net_stats(const FArgs &a, int n, size_t cn, int K) {
@@ -67,9 +61,8 @@ __global__ __launch_bounds__(THREADS) void gprior_frozen_rows_kernel(FArgs a) {
         for (int e = tid; e < G; e += THREADS) dcur[e] = 0.f;
         __syncthreads();
         for (int t = a.S - 1; t >= 0; --t) {                     // the forward's steps, last one first
-            const int s = a.inverse ? a.S - 1 - t : t, code = step_code(a, s);
-            // kept coordinate k of the step sits at kmul * k + kadd, warped coordinate i at kmul * i + wadd
-            const int kmul = code < 2 ? 2 : 1, kadd = code == 0 ? 1 : code == 2 ? K : 0, wadd = code == 1 ? 1 : code == 3 ? K : 0;
+            const int s = a.inverse ? a.S - 1 - t : t;
+            const auto [kmul, kadd, wadd] = step_index(step_code(a.codes, s), K);
             const float *cs = a.canon + (size_t)s * 2 * cn;
             const float *gsrc = step_input(a, s) + (size_t)row * G;
             const size_t at = (size_t)s * BG + (size_t)row * G;          // the row in the (S,B,G) blocks; G = 2K: in w_do too
@@ -210,8 +203,8 @@ __global__ __launch_bounds__(PT) void gprior_frozen_params_kernel(FArgs a) {
         const float *dout = a.w_do + (size_t)s * B * G + br * K;       // + b G + i
         float v;
         if (o < (size_t)nf * K) {                                      // d W0 [j][k] = gamma rstd sum_b dy[b][j] g_keep[b][k]
-            const int j = (int)(o / K), k = (int)(o - (size_t)j * K), code = step_code(a, s);
-            const int kmul = code < 2 ? 2 : 1, kadd = code == 0 ? 1 : code == 2 ? K : 0;
+            const int j = (int)(o / K), k = (int)(o - (size_t)j * K);
+            const auto [kmul, kadd, wadd] = step_index(step_code(a.codes, s), K);
             const float *st = net_stats(a, n, cn, K);
             const float rstd = 1.f / sqrtf(st[nf + j] + a.bn_eps);
             v = a.canon[(size_t)n * cn + (size_t)nf * K + j] * rstd * rows_dot(dy + j, H, step_input(a, s) + kmul * k + kadd, G, B);
@@ -247,10 +240,7 @@ int dpf_gprior_frozen_backward(int n_steps, int B, int G, int n_features, int mo
     if (n_steps <= 0 || n_steps > MAX_STEPS || B < 0 || G < 2 || (G & 1) || n_features <= 0 || !codes || (mode != 0 && mode != 1))
         return DPF_EINVAL;
     FArgs a = {};
-    for (int s = 0; s < n_steps; ++s) {
-        if (codes[s] < 0 || codes[s] > 3) return DPF_EINVAL;
-        a.codes[s >> 4] |= (uint32_t)codes[s] << ((s & 15) * 2);
-    }
+    if (!pack_step_codes(n_steps, codes, a.codes)) return DPF_EINVAL;
     if (B == 0) return 0;
     if (!canon || (params_only && !stats) || !g || !gs || !mus || !lvs || !dg || !dcanon || !workspace) return DPF_EINVAL;
     const int K = G / 2, H = 2 * n_features;

@@ -11,14 +11,11 @@
 #include <stdint.h>
 
 #include "dpf_hip.h"
+#include "gprior_common.h"
 
 namespace {
 
 constexpr int T = 256;
-
-// floats of one net in the canonical block: W0 | gamma | beta | [running_mean | running_var] | W1 | b1  (nbn = 4 with the
-// running-statistics slots of dpf_gprior_pack's layout, 2 in the parameters-only layout)
-inline size_t net_floats(int K, int nf, int nbn) { return (size_t)2 * nf * K + (size_t)nbn * nf + K; }
 
 struct Gemm {          // C[m][n] (+)= sum over `nsum` operand pairs, sum over k:  A[m][k] * Bm[k][n]     (blockIdx.z = batch)
     int M, N, Kd, nsum, accumulate;
@@ -306,8 +303,8 @@ int dpf_gprior_train_forward(int S, int B, int G, int nf, int mode, const int *c
     const size_t cn = net_floats(K, nf, nbn), BG = (size_t)B * G;
     float *hs = workspace, *o = hs + (size_t)B * 2 * nf;
     for (int t = 0; t < S; ++t) {
-        const int s = mode ? S - 1 - t : t, code = codes[s];
-        const int kmul = code < 2 ? 2 : 1, kadd = code == 0 ? 1 : code == 2 ? K : 0, wadd = code == 1 ? 1 : code == 3 ? K : 0;
+        const int s = mode ? S - 1 - t : t;
+        const auto [kmul, kadd, wadd] = step_index(codes[s], K);
         const float *cs = canon + (size_t)s * 2 * cn;
         const float *gin = t == 0 ? g : gs + (size_t)(mode ? s + 1 : s - 1) * BG;
         float *h = save_h + (size_t)s * B * 2 * nf;
@@ -338,8 +335,8 @@ int dpf_gprior_train_backward(int S, int B, int G, int nf, int mode, const int *
     float *hs = workspace, *d_o = hs + BH, *dhs = d_o + BG, *dh = dhs + BH, *run[2] = {dh + BH, dh + BH + BG};
     const float *dcur = nullptr;
     for (int t = S - 1; t >= 0; --t) {                       // the forward's steps, last one first
-        const int s = mode ? S - 1 - t : t, code = codes[s];
-        const int kmul = code < 2 ? 2 : 1, kadd = code == 0 ? 1 : code == 2 ? K : 0, wadd = code == 1 ? 1 : code == 3 ? K : 0;
+        const int s = mode ? S - 1 - t : t;
+        const auto [kmul, kadd, wadd] = step_index(codes[s], K);
         const float *cs = canon + (size_t)s * 2 * cn;
         float *dcs = dcanon + (size_t)s * 2 * cn;
         const float *gin = t == 0 ? g : gs + (size_t)(mode ? s + 1 : s - 1) * BG;

@@ -11,7 +11,7 @@ import torch.nn as nn
 
 from .flows import CondRealNVPFlow3DTriple, EvalAutograd, _needs_autograd, use_hip_training, train_stack, stack_spec, frozen_stack
 from .flowlist import FlowList
-from .layers import PackedWeights
+from .layers import PackedWeights, wants_frozen_hip
 from .engine import FlowStack
 
 
@@ -25,7 +25,7 @@ class LocalCondRNVPDecoder(EvalAutograd, PackedWeights, nn.Module):
             for i in range(n_flows)])
         self.precision = None          # None -> engine.DEFAULT_PRECISION ("f16x3")
         self.materialize_lists = True  # False: skip the 3 x L per-layer tensors (lists then hold the final layer only)
-        # eval_autograd (flows.EvalAutograd): "torch" (default) | "hip" = eval()-mode calls under autograd on the HIP kernels
+        # eval_autograd (layers.EvalAutograd): "torch" (default) | "hip" = eval()-mode calls under autograd on the HIP kernels
 
     def coupling_layers(self):
         """All 3*n_flows CondRealNVPFlow3D modules in DIRECT order."""
@@ -74,8 +74,9 @@ class LocalCondRNVPDecoder(EvalAutograd, PackedWeights, nn.Module):
         if noise is None:
             noise = torch.randn_like(logvar0)                                      # models.py:78
         if self.eval_autograd == "hip":
-            from .frozen_engine import wants_frozen_hip
-            if wants_frozen_hip(self, stack_spec(self, self.coupling_layers()).all_params, noise, mu0, logvar0, g):
+            from .frozen_engine import cuda_fp32
+            if wants_frozen_hip(self, stack_spec(self, self.coupling_layers()).all_params, noise, mu0, logvar0, g) and \
+                    cuda_fp32(noise, mu0, logvar0, g):
                 # the gradient must reach mu0 / logvar0 / noise: z by tensor ops in front of the node
                 z = noise * torch.exp(0.5 * logvar0) + mu0
                 return (z,) + tuple(self.forward(z, g, mode="direct"))

@@ -2,7 +2,7 @@
 
 Under model.eval() the reference's PointNetCloudEncoder followed by the max over the points (lib/networks/encoders.py:15-28,
 models.py:106,124) is differentiable with respect to the cloud and the twelve parameters.  With `eval_autograd = "hip"` such a call
-is ONE autograd node (`_FrozenPool`, modelled on prior_frozen_engine's):
+is ONE autograd node (`_FrozenPool`; the glue it shares with the two flow paths is in networks/layers.py):
 
   forward   the fused eval launch with the argmax switched on (dpf_encoder_forward_arg, csrc/encoder.hip) -- pooled has the bits
             of a no_grad call; saved: x, the canonical block, pooled and the (B,512) argmax, nothing per point;
@@ -13,6 +13,7 @@ The BatchNorm buffers are read, never written.  B = 1 and N = 1 are legal."""
 import torch
 
 from .._lib import lib, check, current_stream, PREC
+from .layers import scatter_param_grads
 
 FROZEN_PRECISIONS = ("bf16x3", "bf16x6")
 
@@ -26,15 +27,23 @@ def frozen_params(enc):
     return out
 
 
-def wants_frozen_hip(enc, x):
-    """True when an eval()-mode call of `enc` asks for the frozen-statistics HIP node: eval_autograd == "hip", grad mode on, and
-    the input or any encoder parameter requires grad."""
-    return (not enc.training) and enc.eval_autograd == "hip" and torch.is_grad_enabled() and \
-        (x.requires_grad or any(p.requires_grad for p in enc.parameters()))
+def frozen_slots(enc):
+    """(offset, numel) of frozen_params in the canonical block (per layer W | gamma | beta | running_mean | running_var), once per module"""
+    slots = enc.__dict__.get("_frozen_slots")
+    if slots is None:
+        slots, off, cin = enc.__dict__.setdefault("_frozen_slots", []), 0, enc.init_n_channels
+        for cout in (enc.init_n_features, *enc.n_features):
+            for n in (cout * cin, cout, cout):
+                slots.append((off, n))
+                off += n
+            off += 2 * cout                                               # the running-statistics slots
+            cin = cout
+        assert off == lib().dpf_encoder_canon_floats(), off
+    return slots
 
 
 def frozen_hip_serves(enc, x):
-    """... and the kernels serve it: the 3 -> 64 -> [128, 256, 512] architecture, CUDA fp32 (B,3,N), bf16x3 or bf16x6."""
+    """What the kernels serve (layers.wants_frozen_hip: what the call asks for): the 3 -> 64 -> [128, 256, 512] architecture, CUDA fp32 (B,3,N), bf16x3 or bf16x6."""
     ts = enc._layer_tensors()
     return enc.hip_supported() and enc.precision in FROZEN_PRECISIONS and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 \
         and x.shape[1] == 3 and x.shape[2] >= 1 and x.shape[0] <= 65535 \
@@ -63,7 +72,7 @@ class _FrozenPool(torch.autograd.Function):
                 check(L_.dpf_encoder_forward_arg(B, N, prec, packed.data_ptr(), x.data_ptr(), pooled.data_ptr(), arg.data_ptr(),
                                                  scratch.data_ptr(), current_stream()), "encoder_forward_arg")
         ctx.save_for_backward(x, canon, packed, pooled, arg)
-        ctx.prec, ctx.shapes = prec, [p.shape for p in params]
+        ctx.prec, ctx.shapes, ctx.slots = prec, [p.shape for p in params], frozen_slots(enc)
         ctx.set_materialize_grads(False)
         return pooled
 
@@ -89,19 +98,8 @@ class _FrozenPool(torch.autograd.Function):
                       "encoder_frozen_backward")
             elif dcanon is not None:
                 dcanon.zero_()
-            grads, off, cin = [], 0, 3
-            for cout in (64, 128, 256, 512):
-                for n in (cout * cin, cout, cout):                        # W, gamma, beta; then the running-statistics slots
-                    grads.append((off, n))
-                    off += n
-                off += 2 * cout
-                cin = cout
-            want = [(o, n, s) for (o, n), s, need in zip(grads, ctx.shapes, needs_p) if need]
-            fresh = [torch.empty(s, dtype=torch.float32, device=dev) for _, _, s in want]
-            if fresh:
-                torch._foreach_copy_(fresh, [dcanon[o:o + n].view(s) for o, n, s in want])
-        it = iter(fresh)
-        return (None, dx) + tuple(next(it) if need else None for need in needs_p)
+            pgrads = scatter_param_grads(dcanon, ctx.slots, ctx.shapes, needs_p)
+        return (None, dx, *pgrads)
 
 
 def run_frozen_pool(enc, x):

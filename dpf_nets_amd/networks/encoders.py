@@ -29,7 +29,7 @@ import torch
 import torch.nn as nn
 
 from .._lib import lib, check, current_stream, PREC
-from .layers import SharedDot, weight_state, EvalModeAutogradWarning
+from .layers import SharedDot, weight_state, EvalAutograd, EvalModeAutogradWarning, wants_frozen_hip
 
 _HIP_ARCH = (3, 64, (128, 256, 512))
 
@@ -258,23 +258,9 @@ class FrozenPointFeatures(PointFeatures):
         return torch.amax(self, dim=dim, keepdim=keepdim)
 
 
-EVAL_AUTOGRAD = ("torch", "hip")
-
-
-class PointNetCloudEncoder(nn.Module):
-    # eval_autograd: "torch" (default) | "hip" = eval()-mode calls under autograd on the HIP kernels with frozen BatchNorm
-    # statistics (csrc/encoder_frozen.hip).  An attribute beside `precision`, not a parameter or buffer: not in the state dict.
-    _eval_autograd = "torch"
-
-    @property
-    def eval_autograd(self):
-        return self._eval_autograd
-
-    @eval_autograd.setter
-    def eval_autograd(self, value):
-        if value not in EVAL_AUTOGRAD:
-            raise ValueError("eval_autograd must be one of %s, got %r" % (list(EVAL_AUTOGRAD), value))
-        self.__dict__["_eval_autograd"] = value
+class PointNetCloudEncoder(EvalAutograd, nn.Module):
+    # eval_autograd (layers.EvalAutograd): "torch" (default) | "hip" = eval()-mode calls under autograd on the HIP kernels with
+    # frozen BatchNorm statistics (csrc/encoder_frozen.hip)
 
     def __init__(self, init_n_channels, init_n_features, n_features):
         super().__init__()
@@ -338,8 +324,8 @@ class PointNetCloudEncoder(nn.Module):
 
     def forward(self, input):
         if self.eval_autograd == "hip":
-            from .encoder_frozen_engine import wants_frozen_hip, frozen_hip_serves
-            if wants_frozen_hip(self, input):
+            from .encoder_frozen_engine import frozen_hip_serves
+            if wants_frozen_hip(self, self.parameters, input):
                 if frozen_hip_serves(self, input):
                     return FrozenPointFeatures(self, input.contiguous())
                 warnings.warn("eval_autograd='hip': this call (CPU tensors, a dtype other than float32, another architecture or "

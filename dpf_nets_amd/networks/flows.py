@@ -18,7 +18,7 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 
-from .layers import SharedDot, Swish, PackedWeights, EvalModeAutogradWarning, _needs_autograd   # noqa: F401  (re-exported)
+from .layers import SharedDot, Swish, PackedWeights, EvalAutograd, EvalModeAutogradWarning, _needs_autograd, wants_frozen_hip   # noqa: F401  (re-exported)
 from .engine import FlowStack
 
 TRAIN_IMPL = os.environ.get("DPF_TRAIN_IMPL", "hip")
@@ -41,33 +41,12 @@ def stack_spec(owner, layers):
     return spec
 
 
-class EvalAutograd:
-    """Mixin: the `eval_autograd` attribute (extension, beside `precision`).  "torch" (default): an eval()-mode call whose inputs
-    require grad is served by tensor operations, with an EvalModeAutogradWarning (layers._needs_autograd).  "hip": an eval()-mode
-    call on CUDA fp32 tensors where p, g or ANY parameter requires grad is one autograd node over the HIP kernels with frozen
-    BatchNorm statistics (networks/frozen_engine.py), no warning.  Setting it on a decoder or a triple reaches the layers."""
-    _eval_autograd = "torch"
-
-    @property
-    def eval_autograd(self):
-        return self._eval_autograd
-
-    @eval_autograd.setter
-    def eval_autograd(self, value):
-        from .frozen_engine import check_eval_autograd
-        self.__dict__["_eval_autograd"] = check_eval_autograd(value)
-        for child in self.children():
-            for m in (child if isinstance(child, nn.ModuleList) else [child]):
-                if isinstance(m, EvalAutograd):
-                    m.eval_autograd = value
-
-
 def frozen_stack(owner, stack, layers, p, g, mode, precision):
     """(ps, mus, lvs) of `layers` through the frozen-statistics HIP node when the call qualifies (eval_autograd == "hip", CUDA fp32,
     something requires grad, the f16x3 stack), else None: the caller goes on as with "torch"."""
-    from .frozen_engine import wants_frozen_hip, run_frozen_stack, frozen_precision_ok
+    from .frozen_engine import cuda_fp32, run_frozen_stack, frozen_precision_ok
     spec = stack_spec(owner, layers)
-    if not wants_frozen_hip(owner, spec.all_params, p, g):
+    if not (wants_frozen_hip(owner, spec.all_params, p, g) and cuda_fp32(p, g)):
         return None
     stack = stack()
     if not frozen_precision_ok(stack, spec, precision, p.device):

@@ -18,25 +18,11 @@ import torch
 
 from .._lib import lib, check, current_stream, PREC, MODE
 from .flowlist import tag_layer_sum
-from .train_engine import F, _T_BR, _grad_table, _scatter
+from .layers import scatter_param_grads
+from .train_engine import F, _T_BR, _grad_table
 
-EVAL_AUTOGRAD = ("torch", "hip")
-
-
-def check_eval_autograd(value):
-    if value not in EVAL_AUTOGRAD:
-        raise ValueError("eval_autograd must be one of %s, got %r" % (list(EVAL_AUTOGRAD), value))
-    return value
-
-
-def wants_frozen_hip(module, spec_params, *tensors):
-    """True when an eval()-mode call of `module` is served by the frozen-statistics HIP node: eval_autograd == "hip", CUDA fp32
-    tensors, grad enabled and ANY of the tensors or of the module's parameters requires grad."""
-    if module.training or module.eval_autograd != "hip" or not torch.is_grad_enabled():
-        return False
-    if not all(t.is_cuda and t.dtype == torch.float32 for t in tensors):
-        return False
-    return any(t.requires_grad for t in tensors) or any(t.requires_grad for t in spec_params())
+def cuda_fp32(*tensors):                      # what the kernels of this path serve (layers.wants_frozen_hip: what the call asks for)
+    return all(t.is_cuda and t.dtype == torch.float32 for t in tensors)
 
 
 def film_frozen_ok(B, G, *blocks):
@@ -201,8 +187,7 @@ class _FlowStackFrozen(torch.autograd.Function):
         views = [flat[o:o + n] for o, n in spec.canon_slots]
         for k in range(4 * spec.L):
             views += [dW0[k], dgam[k], dbet[k], dW1[k], db1[k]]
-        pgrads = _scatter(params, views)
-        pgrads = [t if q else None for t, q in zip(pgrads, ctx.needs_input_grad[6:])]
+        pgrads = scatter_param_grads(views, None, params, ctx.needs_input_grad[6:])
         return (chain if ctx.needs_input_grad[0] else None, dg, None, None, None, None, *pgrads)
 
 

@@ -4,7 +4,8 @@ compatibility) and serve the training-mode path; in eval mode the coupling
 layers read the weights out of them and run the fused HIP stack instead.
 
 Also what every flow module shares around that switch: the packed-weight cache's invalidation (PackedWeights,
-weight_state) and the rule that sends an eval-mode call under autograd to tensor operations (_needs_autograd)."""
+weight_state), the rule that sends an eval-mode call under autograd to tensor operations (_needs_autograd), and what the three
+frozen-statistics HIP paths that replace it on request share: EvalAutograd, wants_frozen_hip, scatter_param_grads."""
 import warnings
 
 import torch
@@ -28,6 +29,51 @@ def _needs_autograd(*tensors):
                       "~30 ATen kernels per coupling layer), not by the fused HIP stack; call under torch.no_grad() for the HIP "
                       "path, or in train() mode for the HIP training kernels", EvalModeAutogradWarning, stacklevel=3)
     return need
+
+
+EVAL_AUTOGRAD = ("torch", "hip")
+
+
+class EvalAutograd:
+    """Mixin: the `eval_autograd` attribute (extension, beside `precision`; not in the state dict).  "torch" (default): an
+    eval()-mode call whose inputs require grad is served by tensor operations, with an EvalModeAutogradWarning (_needs_autograd).
+    "hip": an eval()-mode call on CUDA fp32 tensors where an input or ANY parameter requires grad is one autograd node over the HIP
+    kernels with frozen BatchNorm statistics (networks/*frozen_engine.py), no warning.  Setting it on a decoder or a triple reaches the layers."""
+    _eval_autograd = "torch"
+
+    @property
+    def eval_autograd(self):
+        return self._eval_autograd
+
+    @eval_autograd.setter
+    def eval_autograd(self, value):
+        if value not in EVAL_AUTOGRAD:
+            raise ValueError("eval_autograd must be one of %s, got %r" % (list(EVAL_AUTOGRAD), value))
+        self.__dict__["_eval_autograd"] = value
+        for child in self.children():
+            for m in (child if isinstance(child, nn.ModuleList) else [child]):
+                if isinstance(m, EvalAutograd):
+                    m.eval_autograd = value
+
+
+def wants_frozen_hip(module, params, *tensors):
+    """True when an eval()-mode call of `module` asks for the frozen-statistics HIP node: eval_autograd == "hip", grad mode on, any
+    of `tensors` or of `params()` requires grad.  Whether the kernels serve it (device, dtype, shape, precision) is each path's question."""
+    return (not module.training) and module.eval_autograd == "hip" and torch.is_grad_enabled() and \
+        (any(t.requires_grad for t in tensors) or any(t.requires_grad for t in params()))
+
+
+def scatter_param_grads(block, slots, like, needs=None):
+    """Per entry of `like` (the parameters, or their shapes) a fresh tensor -- never a view: autograd takes it over without a copy
+    -- filled from the (offset, numel) `slots` of the gradient `block` by ONE multi-tensor copy; None where `needs` is false.
+    slots = None: `block` is the list of flat views itself (the point flow's gradients lie in several blocks)."""
+    pick = range(len(like)) if needs is None else [i for i, need in enumerate(needs) if need]
+    fresh = [torch.empty_like(like[i]) if torch.is_tensor(like[i]) else block.new_empty(like[i]) for i in pick]
+    if fresh:
+        src = [block[i] for i in pick] if slots is None else [block[slots[i][0]:slots[i][0] + slots[i][1]] for i in pick]
+        torch._foreach_copy_(fresh, [v.view_as(f) for v, f in zip(src, fresh)])
+    it = iter(fresh)
+    return fresh if needs is None else [next(it) if need else None for need in needs]
 
 
 def weight_state(tensors):

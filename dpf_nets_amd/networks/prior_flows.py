@@ -6,7 +6,7 @@ forward(g, mode):
   * eval mode, CUDA tensors, no autograd (generation / evaluation): the whole stack in ONE HIP launch
     (csrc/gprior.hip through dpf_gprior_forward); the lists come back as views of three (S,B,G) buffers;
   * eval mode under autograd (latent optimisation through log p(g), fine-tuning with frozen statistics): with
-    `eval_autograd = "hip"` on the module (flows.EvalAutograd; a container hands it to the modules below it) a call on CUDA
+    `eval_autograd = "hip"` on the module (layers.EvalAutograd; a container hands it to the modules below it) a call on CUDA
     fp32 tensors where g OR ANY PARAMETER requires grad is one autograd node -- that same launch forward, two launches
     backward whatever the number of steps (csrc/gprior_frozen.hip through networks/prior_frozen_engine.py); the BatchNorm
     buffers are only read and B = 1 is legal.  With the default "torch" a call whose g requires grad is the tensor-op
@@ -24,11 +24,10 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .layers import Swish, PackedWeights, weight_state, _needs_autograd
+from .layers import Swish, PackedWeights, EvalAutograd, weight_state, _needs_autograd, wants_frozen_hip, scatter_param_grads
 from .flat_store import ParamStore
 from .flowlist import FlowList, tag_layer_sum
 from .train_engine import update_running_stats
-from .flows import EvalAutograd
 from .._lib import lib, check, current_stream, MODE
 
 
@@ -232,7 +231,7 @@ def _stack_plan(module, layers):
     canonical block, the BatchNorm modules, the block's floats, the kernel's step codes, (S, G, nf), RealNVPFlow's eps)."""
     plan = module.__dict__.get("_train_plan")
     if plan is None:
-        params, slots, bns, total = _step_params(layers)
+        params, slots, bns, total = _net_walk(layers, True)
         S, G, nf = len(layers), layers[0].g_n_features, layers[0].n_features
         codes = (ctypes.c_int * S)(*[pattern_code(l.warp_inds, G) for l in layers])
         assert total == S * lib().dpf_gprior_canon_floats(G, nf)
@@ -244,14 +243,11 @@ def _frozen_prior(module, layers, g, mode):
     """(gs, mus, lvs) of `layers` (DIRECT order) through the frozen-statistics HIP node when the call qualifies -- eval_autograd ==
     "hip", eval mode, a CUDA fp32 g, grad enabled, g or any parameter of the stack requires grad, the kernel's index patterns --
     else None: the caller goes on as with "torch".  Three python lists as the training path returns them."""
-    if module.eval_autograd != "hip" or module.training or not layers or not g.is_cuda or g.dtype != torch.float32 \
-            or not torch.is_grad_enabled() or not _patterns_ok(module, layers):
+    if module.eval_autograd != "hip" or not layers or not g.is_cuda or g.dtype != torch.float32 or not _patterns_ok(module, layers) \
+            or not wants_frozen_hip(module, lambda: _stack_plan(module, layers)[0], g):
         return None
-    from .frozen_engine import wants_frozen_hip
     from .prior_frozen_engine import run_frozen_prior
     params, slots, bns, total, codes, dims, eps = _stack_plan(module, layers)
-    if not wants_frozen_hip(module, lambda: params, g):
-        return None
     if g.dim() != 2 or g.shape[1] != dims[1]:
         raise RuntimeError("expected g (B,%d)" % dims[1])
     stack = module.packed_stack(lambda: GPriorStack(layers))
@@ -267,16 +263,16 @@ def _frozen_prior(module, layers, g, mode):
     return list(gs.unbind(0)), list(mus.unbind(0)), tag_layer_sum(list(lvs.unbind(0)), sum_lv)
 
 
-def _step_params(layers):
-    """Every step's tensors in the canonical order; (parameters, their slots in the canon block, the BatchNorm modules)."""
+def _net_walk(layers, stats_slots):
+    """Every net's tensors in the canonical order -> (parameters, their (offset, numel) slots, the BatchNorm modules, the block's
+    floats).  stats_slots: running_mean | running_var, not parameters, keep their place behind beta (dpf_gprior_pack's layout)."""
     params, slots, bns, off = [], [], [], 0
     for l in layers:
         for br in ("mu", "logvar"):
             net = getattr(l, "T_%s_0" % br)
-            for t in (net[0].weight, net[1].weight, net[1].bias):
-                params.append(t); slots.append((off, t.numel())); off += t.numel()
-            off += 2 * net[1].num_features                             # running_mean | running_var: not parameters
-            for t in (net[3].weight, net[3].bias):
+            for t in (net[0].weight, net[1].weight, net[1].bias, net[3].weight, net[3].bias):
+                if stats_slots and t is net[3].weight:
+                    off += 2 * net[1].num_features
                 params.append(t); slots.append((off, t.numel())); off += t.numel()
             bns.append(net[1])
     return params, slots, bns, off
@@ -318,13 +314,8 @@ class PriorFlatStore(ParamStore):
     data-parallel exchange is one all-reduce (distributed.allreduce_flat_gradients)."""
 
     def __init__(self, layers, dev):
-        params, slots, off = [], [], 0
-        for l in layers:
-            for br in ("mu", "logvar"):
-                net = getattr(l, "T_%s_0" % br)
-                for t in (net[0].weight, net[1].weight, net[1].bias, net[3].weight, net[3].bias):
-                    params.append(t); slots.append((off, t.numel())); off += t.numel()
-        super().__init__(params, slots, off, dev)
+        params, slots, _, total = _net_walk(layers, False)
+        super().__init__(params, slots, total, dev)
 
     def accumulate(self, dcanon):
         self.attach_grads()
@@ -377,8 +368,7 @@ class _GPriorTrain(torch.autograd.Function):
         params = ctx.saved_tensors[7:]
         mode, codes, dims, bn_eps, eps, slots = ctx.cfg
         dg, dcanon = _train_backward(g, canon, 0, gs, mus, lvs, save_h, stats, (d_gs, d_mus, d_lvs), mode, codes, dims, bn_eps, eps)
-        grads = [torch.empty_like(p) for p in params]
-        torch._foreach_copy_(grads, [dcanon[o:o + n].view_as(p) for (o, n), p in zip(slots, params)])
+        grads = scatter_param_grads(dcanon, slots, params)
         return (dg if ctx.needs_input_grad[0] else None, None, None, None, None, None, None, None, *grads)
 
 

@@ -13,6 +13,7 @@ The BatchNorm buffers are read, never written.  B = 1 is legal."""
 import torch
 
 from .._lib import lib, check, current_stream, MODE
+from .layers import scatter_param_grads
 
 
 def _forward(stack, g, mode):
@@ -60,12 +61,7 @@ class _GPriorFrozen(torch.autograd.Function):
         g, canon, gs, mus, lvs = ctx.saved_tensors[:5]
         params = ctx.saved_tensors[5:]
         dg, dcanon = _backward(ctx.cfg, canon, 0, None, g, gs, mus, lvs, grads)
-        want = [(p, o, n) for p, (o, n), need in zip(params, ctx.slots, ctx.needs_input_grad[4:]) if need]
-        fresh = [torch.empty_like(p) for p, _, _ in want]
-        if fresh:
-            torch._foreach_copy_(fresh, [dcanon[o:o + n].view_as(p) for p, o, n in want])
-        it = iter(fresh)
-        pgrads = [next(it) if need else None for need in ctx.needs_input_grad[4:]]
+        pgrads = scatter_param_grads(dcanon, ctx.slots, params, ctx.needs_input_grad[4:])
         return (dg if ctx.needs_input_grad[0] else None, None, None, None, *pgrads)
 
 

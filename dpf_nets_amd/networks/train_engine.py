@@ -28,6 +28,7 @@ from .._lib import lib, check, current_stream, PREC, MODE
 from .engine import layer_meta
 from .flat_store import ParamStore, hook_grad_written            # noqa: F401  (hook_grad_written: re-exported)
 from .flowlist import tag_layer_sum
+from .layers import scatter_param_grads
 
 F = 64
 # precision of the forward contraction and of its recomputation in the backward passes (which fixes
@@ -199,13 +200,6 @@ def update_running_stats(bns, means, uvars):
     torch._foreach_mul_(rvs, 1.0 - m)
     torch._foreach_add_(rvs, uvars, alpha=m)
     torch._foreach_add_(nbt, 1)
-
-
-def _scatter(shapes_like, flat_views):
-    """Fresh gradient tensors (autograd takes them over without a copy) filled by one multi-tensor copy."""
-    outs = [torch.empty_like(t) for t in shapes_like]
-    torch._foreach_copy_(outs, [v.view_as(o) for v, o in zip(flat_views, outs)])
-    return outs
 
 
 def _forward_core(p, g, spec, mode, prec, tcanon, W0, gam, bet, W1, b1, flat=None):
@@ -402,7 +396,7 @@ class _FlowStackTrain(torch.autograd.Function):
         views = [flat[o:o + n] for o, n in spec.canon_slots]
         for k in range(4 * spec.L):
             views += [dW0[k], dgam[k], dbet[k], dW1[k], db1[k]]
-        grads = _scatter(params, views)
+        grads = scatter_param_grads(views, None, params)
         return (chain if ctx.needs_input_grad[0] else None, dg, None, None, None, *grads)
 
 
