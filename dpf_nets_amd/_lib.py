@@ -110,6 +110,11 @@ SIGNATURES = {
     "dpf_occupancy_max_res": (_i, []),
     "dpf_occupancy_grid_workspace_bytes": (_sz, [_i, _i, _i]),
     "dpf_occupancy_grid": (_i, [_i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dpf_mesh_cdf_tile": (_i, []),
+    "dpf_mesh_cdf_workspace_bytes": (_sz, [_i, _l]),
+    "dpf_mesh_cdf_build": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _sz, _vp]),
+    "dpf_mesh_variates": (_i, [_i, _i, ctypes.c_ulonglong, ctypes.c_ulonglong, _vp, _vp, _vp, _vp]),
+    "dpf_mesh_sample": (_i, [_i] + [_vp] * 8 + [_i, _i] + [_vp] * 4 + [_i, _i, _f, _f, _f, _f] + [_vp] * 4),
     "dpf_version": (ctypes.c_char_p, []),
 }
 

@@ -698,6 +698,43 @@ int dpf_occupancy_grid(int S, int n, const float *clouds, int res, int mode, con
                        unsigned int *clouds_touching, unsigned int *flags, void *workspace, size_t workspace_bytes,
                        dpf_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * Mesh surface sampling into the collated training batch (csrc/mesh_sample.hip; lib/datasets/cloud_sampling.py:4-32 and the
+ * elementwise transforms of lib/datasets/cloud_transformations.py).  The mesh store, all device memory, mirrors meshes.h5:
+ * vertices (sum V, 3) fp32, faces (sum F, 3) uint32 with indices LOCAL to their mesh, vertex_bounds / face_bounds of M + 1
+ * increasing int64 entries starting at 0; every mesh has at least one face and fewer than 2^31.
+ *   dpf_mesh_cdf_build: cdf (sum F) doubles, flags (M) words.  Face area in fp32 as numpy forms it (e1 = p2 - p0, e2 = p2 - p1,
+ *     cross product as a product minus a product, sqrt((c0*c0 + c1*c1) + c2*c2) / 2, nothing fused).  cdf[f] of mesh m =
+ *     (sum of its faces 0..f) / (sum of all its faces) in double, summed in tiles of dpf_mesh_cdf_tile() faces counted from
+ *     the mesh's first face: inside a tile one after the other in face order, the tile totals one after the other, edge =
+ *     (tile offset + sum inside the tile) / total.  The bits depend on the mesh alone; the edges never decrease and the last is 1.
+ *     tile_bounds: (M + 1) int64, tile_bounds[m + 1] - tile_bounds[m] = ceil(F_m / tile); n_tiles = tile_bounds[M].
+ *     flags[m]: bit 0 a face index >= V_m (the vertex is not read), bit 1 a non-finite area, bit 2 a total of zero; such faces
+ *     count as area 0 and the cdf of a flagged mesh is zeroed.  workspace: the workspace_bytes query, 8-byte aligned; free
+ *     after the call's work has run.  The caller reads flags back once -- the store's only synchronisation.
+ *   dpf_mesh_variates: u (B, S) double with 53 random bits, s1 / s2 (B, S) fp32 = the double uniform rounded to fp32, from
+ *     splitmix64 keyed by (seed, step, slot, sample, stream): base = mix(mix(seed) ^ step), slot key = mix(base ^ b),
+ *     bits = mix(slot key ^ (4 * i + stream)), uniform = (bits >> 11) * 2^-53.  Equal meshes in two slots draw different streams.
+ *   dpf_mesh_sample: B slots of S samples; mesh_idx (B) int32.  face = the first k with cdf[k] > u (searchsorted side='right');
+ *     if (s1 + s2 > 1) { s1 = 1 - s1; s2 = 1 - s2; }; point = (p0 + s1 * (p1 - p0)) + s2 * (p2 - p0); then, by the bits of
+ *     xform: 1 `orig_s[m] * x`, 2 `+ orig_c[m][axis]`, 4 `- shift[axis]`, 8 `/ scale` -- all fp32, each rounded on its own.
+ *     split = 0: cloud (B, 3, S).  split = 1 (S even): even samples to cloud, odd ones to eval_cloud, each (B, 3, S / 2).
+ *     faces_out: optional (B, S) int32.  u must lie in [0, 1).  A slot whose mesh index is outside the store or whose mesh is
+ *     flagged reads nothing of the mesh: NaN points, face -1.  Launches on the caller's stream, never synchronises; B and S are
+ *     chunked over launches. */
+int dpf_mesh_cdf_tile(void);
+size_t dpf_mesh_cdf_workspace_bytes(int M, long n_tiles);
+int dpf_mesh_cdf_build(int M, const float *vertices, const long *vertex_bounds, const unsigned int *faces,
+                       const long *face_bounds, const long *tile_bounds, long n_tiles, double *cdf, unsigned int *flags,
+                       void *workspace, size_t workspace_bytes, dpf_stream_t stream);
+int dpf_mesh_variates(int B, int S, unsigned long long seed, unsigned long long step, double *u, float *s1, float *s2,
+                      dpf_stream_t stream);
+int dpf_mesh_sample(int M, const float *vertices, const long *vertex_bounds, const unsigned int *faces,
+                    const long *face_bounds, const double *cdf, const unsigned int *flags, const float *orig_c,
+                    const float *orig_s, int B, int S, const int *mesh_idx, const double *u, const float *s1,
+                    const float *s2, int split, int xform, float shift_x, float shift_y, float shift_z, float scale,
+                    float *cloud, float *eval_cloud, int *faces_out, dpf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
