@@ -45,7 +45,7 @@ typedef uint32_t u4a __attribute__((ext_vector_type(4), aligned(4)));   // 16 by
 
 constexpr int CH = 8;            // candidates per min-chunk
 constexpr int NWAVES = 4;        // waves per workgroup (default; the small-problem variants use 8 and 16)
-constexpr int QPW = 128;         // query points per wave (2 per lane)
+constexpr int QPW = dispatch::NN_QPW;      // query points per wave (2 per lane): 128
 
 struct NNDir {
     const float *q;   // (B, nq, 3) queries
@@ -529,29 +529,11 @@ __global__ __launch_bounds__(RT) void fscore_kernel(int n, int m, const float *_
 
 }  // namespace
 
-// -1 (default): by size; 0: never; 1: whenever the clouds fit (tests / measurements).  env DPF_NN_SMALL.
-static int g_nn_small_mode = getenv("DPF_NN_SMALL") ? atoi(getenv("DPF_NN_SMALL")) : -1;
-extern "C" int dpf_nn_small_mode(int mode) {
-    const int old = g_nn_small_mode;
-    g_nn_small_mode = mode < 0 ? -1 : (mode ? 1 : 0);
-    return old;
-}
+// -1 (default): by size; 0: never; 1: whenever the clouds fit (tests / measurements).  Returns the old mode.
+extern "C" int dpf_nn_small_mode(int mode) { return dispatch::set_mode(dispatch::settable().nn_small, mode); }
 
-// rank-sized batches of mid-sized clouds: the LDS-staged kernel.  One workgroup per CU or fewer (B = 4 clouds of 2048 points:
-// 10.4 us against the scalar-load scan's 14.9); with more the CUs that hold two workgroups set the pace and the scan that
-// streams its candidates through SGPRs is as fast (B = 8: 16.0 vs 15.9 us; r04_small/sweep.txt).
-bool nn_small_serves(int b, int n, int m) {       // (also asked by chamfer_mfma.hip's choice of kernel)
-    const int nmax = n > m ? n : m, minc = n < m ? n : m;
-    if (g_nn_small_mode == 0 || nmax > 8192 || b > 65535) return false;
-    if (g_nn_small_mode == 1) return true;
-    return minc >= 1024 && (long)((nmax + 63) / 64) * b * 2 <= 256;
-}
-static int nn_small_launch(const NNArgs &a, int b, int nmax, hipStream_t s) {
+static int nn_small_launch(const NNArgs &a, int b, int nmax, int ksw, hipStream_t s) {
     const int lds = 3 * ((nmax + 7) & ~7) * (int)sizeof(float);
-    // candidate slices per workgroup: enough waves for two per SIMD (a lone wave is bound by its own issue rate)
-    static const int ksw_env = getenv("DPF_NN_KSW") ? atoi(getenv("DPF_NN_KSW")) : 0;
-    const long wgs = (long)((nmax + 63) / 64) * b * 2;
-    const int ksw = ksw_env ? ksw_env : (wgs * 4 >= 2048 ? 4 : 8);
     const dim3 grid((nmax + 63) / 64, b, 2);
     static LdsLimit limit4, limit8, limit16;
     if (ksw == 4) {
@@ -570,15 +552,15 @@ static int nn_small_launch(const NNArgs &a, int b, int nmax, hipStream_t s) {
 // dpf_nndistance_cd's fast path for the same problems (chamfer_mfma.hip): DPF_ENOSUP when the kernel does not serve them.
 // workspace layout as there: b tickets (zero on entry and on exit), then 2 * ceil(nmax / 64) sums per cloud.
 int nn_small_cd(int b, int n, const float *xyz, int m, const float *xyz2, float *result, int *result_i, float *result2,
-                int *result2_i, float *cd, void *workspace, int tickets_are_zero, hipStream_t s) {
-    if (!nn_small_serves(b, n, m)) return DPF_ENOSUP;
+                int *result2_i, float *cd, void *workspace, int tickets_are_zero, const dispatch::Switches &sw, hipStream_t s) {
+    if (!dispatch::nn_small_serves(b, n, m, sw)) return DPF_ENOSUP;
     if (!tickets_are_zero)
         if (hipError_t e = dpf_zero_async(workspace, (size_t)b * sizeof(unsigned), s); e != hipSuccess) return (int)e;
     NNArgs a;
     a.d[0] = NNDir{xyz, xyz2, result, result_i, n, m, (long)n * 3, (long)m * 3};
     a.d[1] = NNDir{xyz2, xyz, result2, result2_i, m, n, (long)m * 3, (long)n * 3};
     a.ticket = (unsigned *)workspace; a.part = (float *)workspace + b; a.cd = cd;
-    return nn_small_launch(a, b, n > m ? n : m, s);
+    return nn_small_launch(a, b, n > m ? n : m, dispatch::nn_small_ksw(b, n > m ? n : m, sw), s);
 }
 
 extern "C" int dpf_fscore_reduce(int b, int n, int m, const float *dist1, const float *dist2, float threshold, float *out,
@@ -599,12 +581,9 @@ extern "C" int dpf_chamfer_reduce(int b, int n, int m, const float *dist1, const
     return (int)hipGetLastError();
 }
 
-// nndistance with explicit per-cloud strides (in floats): stride 0 broadcasts ONE cloud against a
-// whole batch, which is what pairwise_CD needs (lib/networks/utils.py:104-107 expands and copies
-// cloud i N2 times before every call).
-extern "C" int dpf_nndistance_strided(int b, int n, const float *xyz, long xyz_stride, int m, const float *xyz2,
-                                      long xyz2_stride, float *result, int *result_i, float *result2, int *result2_i,
-                                      dpf_stream_t stream) {
+// dpf_nndistance_strided's checks and launches, with the caller's switches
+int nn_scan_strided(int b, int n, const float *xyz, long xyz_stride, int m, const float *xyz2, long xyz2_stride, float *result,
+                    int *result_i, float *result2, int *result2_i, const dispatch::Switches &sw, hipStream_t s) {
     if (b < 0 || n <= 0 || m <= 0 || xyz_stride < 0 || xyz2_stride < 0) return DPF_EINVAL;
     if (b == 0) return 0;
     if (!xyz || !xyz2 || !result || !result_i || !result2 || !result2_i) return DPF_EINVAL;
@@ -613,40 +592,37 @@ extern "C" int dpf_nndistance_strided(int b, int n, const float *xyz, long xyz_s
     a.d[0] = NNDir{xyz, xyz2, result, result_i, n, m, xyz_stride, xyz2_stride};     // nndistance.cu:126
     a.d[1] = NNDir{xyz2, xyz, result2, result2_i, m, n, xyz2_stride, xyz_stride};   // nndistance.cu:127
     const int nmax = n > m ? n : m;
-    // pick the candidate split so that the launch has >= ~2 waves per SIMD on 256 CUs
-    const long waves1 = (long)b * ((n + QPW - 1) / QPW + (m + QPW - 1) / QPW);
-    hipStream_t s = (hipStream_t)stream;
-    // Small problems (a rank's 4-8 clouds of 2048 points): with one wave per SIMD the scan is bound by the LATENCY of its
-    // scalar loads (one chunk of prefetch covers ~300 cycles of VALU work, an L2-served s_load takes longer), so the
-    // candidates are split over MORE waves -- 8 or 16 slices merged in LDS in ascending order -- until every SIMD has two
-    static const int ks_env = getenv("DPF_NN_KS") ? atoi(getenv("DPF_NN_KS")) : 0;
-    const int minc = n < m ? n : m;
-    if (nn_small_serves(b, n, m) && !ks_env) return nn_small_launch(a, b, nmax, s);
-    int ks_small = ks_env;
-    if (!ks_small && waves1 < 512 && minc >= 1024) ks_small = 8;    // r04, B=4 N=2048: 4 slices 18.4 us, 8: 15.3, 16: 16.8
-    if (ks_small == 16 || ks_small == 8) {
+    const dispatch::NNForm form = dispatch::nn_form(b, n, m, sw);
+    if (form.kernel == dispatch::NNKernel::Staged) return nn_small_launch(a, b, nmax, form.width, s);
+    if (form.kernel == dispatch::NNKernel::Sliced) {
         dim3 grid((nmax + QPW - 1) / QPW, b, 2);
-        if (ks_small == 16) hipLaunchKernelGGL((nn_kernel<16, 16>), grid, dim3(16 * 64), 0, s, a);
+        if (form.width == 16) hipLaunchKernelGGL((nn_kernel<16, 16>), grid, dim3(16 * 64), 0, s, a);
         else hipLaunchKernelGGL((nn_kernel<8, 8>), grid, dim3(8 * 64), 0, s, a);
         return (int)hipGetLastError();
     }
-    if (waves1 >= 2048 || (n < 64 && m < 64)) {
-        dim3 grid((nmax + NWAVES * QPW - 1) / (NWAVES * QPW), b, 2);
-        hipLaunchKernelGGL(nn_kernel<1>, grid, dim3(NWAVES * 64), 0, s, a);
-    } else if (waves1 >= 1024) {
-        dim3 grid((nmax + 2 * QPW - 1) / (2 * QPW), b, 2);
-        hipLaunchKernelGGL(nn_kernel<2>, grid, dim3(NWAVES * 64), 0, s, a);
-    } else {
-        dim3 grid((nmax + QPW - 1) / QPW, b, 2);
-        hipLaunchKernelGGL(nn_kernel<4>, grid, dim3(NWAVES * 64), 0, s, a);
+    const dim3 grid((nmax + (NWAVES / form.width) * QPW - 1) / ((NWAVES / form.width) * QPW), b, 2);
+    switch (form.width) {                                // candidate slices over the workgroup's 4 waves
+    case 1: hipLaunchKernelGGL(nn_kernel<1>, grid, dim3(NWAVES * 64), 0, s, a); break;
+    case 2: hipLaunchKernelGGL(nn_kernel<2>, grid, dim3(NWAVES * 64), 0, s, a); break;
+    default: hipLaunchKernelGGL(nn_kernel<4>, grid, dim3(NWAVES * 64), 0, s, a); break;
     }
     return (int)hipGetLastError();
 }
 
+// nndistance with explicit per-cloud strides (in floats): stride 0 broadcasts ONE cloud against a
+// whole batch, which is what pairwise_CD needs (lib/networks/utils.py:104-107 expands and copies
+// cloud i N2 times before every call).
+extern "C" int dpf_nndistance_strided(int b, int n, const float *xyz, long xyz_stride, int m, const float *xyz2,
+                                      long xyz2_stride, float *result, int *result_i, float *result2, int *result2_i,
+                                      dpf_stream_t stream) {
+    return nn_scan_strided(b, n, xyz, xyz_stride, m, xyz2, xyz2_stride, result, result_i, result2, result2_i, dispatch::snapshot(),
+                           (hipStream_t)stream);
+}
+
 extern "C" int dpf_nndistance(int b, int n, const float *xyz, int m, const float *xyz2, float *result, int *result_i,
                               float *result2, int *result2_i, dpf_stream_t stream) {
-    return dpf_nndistance_strided(b, n, xyz, (long)n * 3, m, xyz2, (long)m * 3, result, result_i, result2, result2_i,
-                                  stream);
+    return nn_scan_strided(b, n, xyz, (long)n * 3, m, xyz2, (long)m * 3, result, result_i, result2, result2_i, dispatch::snapshot(),
+                           (hipStream_t)stream);
 }
 
 extern "C" int dpf_nndistancegrad(int b, int n, const float *xyz1, int m, const float *xyz2, const float *grad_dist1,

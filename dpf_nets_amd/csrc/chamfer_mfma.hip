@@ -55,7 +55,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // waves per workgroup (32 queries each): template parameter QW = 16, or 8 when that is what fills the chip
-constexpr int CT = 64;           // candidate tiles resident in LDS at a time (64 KiB of fragments + 25 KiB of points)
+constexpr int CT = dispatch::NNM_CT;           // candidate tiles resident in LDS at a time (64 KiB of fragments + 25 KiB of points)
 // points of a tile in LDS: x[32] | y[32] | z[32] | 4 floats of padding.  The exact evaluations read the tiles their lanes'
 // survivors name -- any tiles -- at the same offset inside the tile: r04's rows of 32 float4 (512 B apart) put every one of
 // those reads on the same four banks (counters: SQ_LDS_BANK_CONFLICT = a third of SQ_LDS_IDX_ACTIVE).  r05: rows of 100
@@ -694,10 +694,6 @@ static unsigned long long *g_nnm_prof = nullptr;
 extern "C" void dpf_debug_set_nnm_prof(void *p) { g_nnm_prof = (unsigned long long *)p; }
 #endif
 
-static long nnm_workgroups(int b, int n, int m, int qw) {
-    return (long)b * ((n + qw * 32 - 1) / (qw * 32) + (m + qw * 32 - 1) / (qw * 32));
-}
-
 template <int QW>
 static int launch_nnm_qw(const MArgs &ma, int b, int nmax, hipStream_t s) {
     // (the grid's x extent is the stride of the partial sums when ma.part is set)
@@ -708,11 +704,10 @@ static int launch_nnm_qw(const MArgs &ma, int b, int nmax, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
-// 16 waves (512 queries) per workgroup share one build of the candidates' fragments; when that leaves fewer than 128
-// workgroups (small batches of big clouds, e.g. B = 2, N = 8192 per GPU in cfg-5) 8-wave workgroups fill twice the CUs
-static int launch_nnm(int b, int n, const float *xyz, long xyz_stride, int m, const float *xyz2, long xyz2_stride,
-                      float *result, int *result_i, float *result2, int *result2_i, hipStream_t s, float *part = nullptr,
-                      bool force16 = false, unsigned *ticket = nullptr, float *cd = nullptr) {
+// the workgroup's waves: dispatch.h's nnm_qw
+static int launch_nnm(int b, int n, const float *xyz, long xyz_stride, int m, const float *xyz2, long xyz2_stride, float *result,
+                      int *result_i, float *result2, int *result2_i, const dispatch::Switches &sw, hipStream_t s,
+                      float *part = nullptr, bool force16 = false, unsigned *ticket = nullptr, float *cd = nullptr) {
     MArgs ma;
     ma.pn2 = 0; ma.part = part; ma.ticket = ticket; ma.cd = cd;
 #ifdef DPF_PROFILE
@@ -721,28 +716,20 @@ static int launch_nnm(int b, int n, const float *xyz, long xyz_stride, int m, co
     ma.d[0] = MDir{xyz, xyz2, result, result_i, n, m, xyz_stride, xyz2_stride};       // nndistance.cu:126
     ma.d[1] = MDir{xyz2, xyz, result2, result2_i, m, n, xyz2_stride, xyz_stride};     // nndistance.cu:127
     const int nmax = n > m ? n : m;
-    static const int qw_env = getenv("DPF_NNM_QW") ? atoi(getenv("DPF_NNM_QW")) : 0;      // experiments: 4 | 8 | 16
-    if (force16 || qw_env == 16) return launch_nnm_qw<16>(ma, b, nmax, s);
-    if (qw_env == 8) return launch_nnm_qw<8>(ma, b, nmax, s);
-    if (qw_env == 4) return launch_nnm_qw<4>(ma, b, nmax, s);
-    if (nnm_workgroups(b, n, m, 16) >= 128) return launch_nnm_qw<16>(ma, b, nmax, s);
-    return nnm_workgroups(b, n, m, 8) >= 128 ? launch_nnm_qw<8>(ma, b, nmax, s) : launch_nnm_qw<4>(ma, b, nmax, s);
+    switch (dispatch::nnm_qw(b, n, m, force16, sw)) {
+    case 16: return launch_nnm_qw<16>(ma, b, nmax, s);
+    case 8: return launch_nnm_qw<8>(ma, b, nmax, s);
+    default: return launch_nnm_qw<4>(ma, b, nmax, s);
+    }
 }
 
-// enough pairs to amortise building the fragments and enough workgroups to fill the chip (r01, tools/nn_impl_sweep.py:
-// 25 vs 52 us at B=32, n=m=2048; 76 vs 190 us at B=8, n=m=8192; 50 vs 64 us at B=2, n=m=8192); small clouds and small
-// batches are launch-bound either way and few workgroups leave the matrix cores idle
-// r04, after the filter's bookkeeping was rebuilt (see nnm_kernel): it also wins for mid-sized batches of clouds whose
-// fragments fit one pass -- B = 6 / 8 / 10 clouds of 2048: 13.4 / 12.0 / 12.1 us against the scans' 15.2 / 15.3 / 24.4; 16 clouds
-// of 1024: 8.2 vs 10.0 -- but not where the LDS-staged scan serves (one workgroup per CU or fewer: B = 4: 10.4 vs 13.3) and not
-// for clouds a little over one pass (B = 4, N = 2500: 22.8 vs 17.3).
-bool nn_small_serves(int b, int n, int m);      // chamfer.hip
-static bool nnm_pays(int b, int n, int m) {
-    if (b <= 0 || n <= 0 || m <= 0 || b > 65535 || n > 65535 * 32 || m > 65535 * 32) return false;
-    if (nnm_workgroups(b, n, m, 8) < 64) return false;                // B=1, n=m=8192: 48 vs 57 us
-    const double pairs = 2.0 * (double)b * (double)n * (double)m;
-    if (pairs >= 1.0e8) return true;
-    return pairs >= 3.0e7 && (n > m ? n : m) <= CT * 32 && !nn_small_serves(b, n, m);
+// the matrix-core filter where it pays (dispatch.h's nnm_pays), dpf_nndistance_strided's scan otherwise: one choice, from the
+// switches the entry read
+static int nn_auto(int b, int n, const float *xyz, long xyz_stride, int m, const float *xyz2, long xyz2_stride, float *result,
+                   int *result_i, float *result2, int *result2_i, const dispatch::Switches &sw, hipStream_t s) {
+    if (xyz && xyz2 && result && result_i && result2 && result2_i && xyz_stride >= 0 && xyz2_stride >= 0 && dispatch::nnm_pays(b, n, m, sw))
+        return launch_nnm(b, n, xyz, xyz_stride, m, xyz2, xyz2_stride, result, result_i, result2, result2_i, sw, s);
+    return nn_scan_strided(b, n, xyz, xyz_stride, m, xyz2, xyz2_stride, result, result_i, result2, result2_i, sw, s);
 }
 
 extern "C" int dpf_nndistance_mfma(int b, int n, const float *xyz, int m, const float *xyz2, float *result,
@@ -752,18 +739,18 @@ extern "C" int dpf_nndistance_mfma(int b, int n, const float *xyz, int m, const 
     if (b < 0 || n <= 0 || m <= 0) return DPF_EINVAL;
     if (b == 0) return 0;
     if (!xyz || !xyz2 || !result || !result_i || !result2 || !result2_i) return DPF_EINVAL;
+    const dispatch::Switches sw = dispatch::snapshot();
     if (b > 65535 || n > 65535 * 32 || m > 65535 * 32 || (n < 32 && m < 32))
-        return dpf_nndistance(b, n, xyz, m, xyz2, result, result_i, result2, result2_i, stream);
-    return launch_nnm(b, n, xyz, (long)n * 3, m, xyz2, (long)m * 3, result, result_i, result2, result2_i, (hipStream_t)stream);
+        return nn_scan_strided(b, n, xyz, (long)n * 3, m, xyz2, (long)m * 3, result, result_i, result2, result2_i, sw, (hipStream_t)stream);
+    return launch_nnm(b, n, xyz, (long)n * 3, m, xyz2, (long)m * 3, result, result_i, result2, result2_i, sw, (hipStream_t)stream);
 }
 
 // Same contract and the same bits as dpf_nndistance; the matrix-core filtered kernel where it measured faster, the
 // VALU scan otherwise.
 extern "C" int dpf_nndistance_auto(int b, int n, const float *xyz, int m, const float *xyz2, float *result, int *result_i,
                                    float *result2, int *result2_i, dpf_stream_t stream) {
-    if (xyz && xyz2 && result && result_i && result2 && result2_i && nnm_pays(b, n, m))
-        return launch_nnm(b, n, xyz, (long)n * 3, m, xyz2, (long)m * 3, result, result_i, result2, result2_i, (hipStream_t)stream);
-    return dpf_nndistance(b, n, xyz, m, xyz2, result, result_i, result2, result2_i, stream);
+    return nn_auto(b, n, xyz, (long)n * 3, m, xyz2, (long)m * 3, result, result_i, result2, result2_i, dispatch::snapshot(),
+                   (hipStream_t)stream);
 }
 
 // dpf_nndistance_strided's contract and bits (explicit per-cloud strides, 0 = broadcast: one row of pairwise_CD per
@@ -771,9 +758,8 @@ extern "C" int dpf_nndistance_auto(int b, int n, const float *xyz, int m, const 
 extern "C" int dpf_nndistance_strided_auto(int b, int n, const float *xyz, long xyz_stride, int m, const float *xyz2,
                                            long xyz2_stride, float *result, int *result_i, float *result2, int *result2_i,
                                            dpf_stream_t stream) {
-    if (xyz && xyz2 && result && result_i && result2 && result2_i && xyz_stride >= 0 && xyz2_stride >= 0 && nnm_pays(b, n, m))
-        return launch_nnm(b, n, xyz, xyz_stride, m, xyz2, xyz2_stride, result, result_i, result2, result2_i, (hipStream_t)stream);
-    return dpf_nndistance_strided(b, n, xyz, xyz_stride, m, xyz2, xyz2_stride, result, result_i, result2, result2_i, stream);
+    return nn_auto(b, n, xyz, xyz_stride, m, xyz2, xyz2_stride, result, result_i, result2, result2_i, dispatch::snapshot(),
+                   (hipStream_t)stream);
 }
 
 // The whole (N1, N2) Chamfer-distance matrix of lib/networks/utils.py:90-117 (pairwise_CD) in ONE launch (+ one tiny finish):
@@ -782,10 +768,9 @@ extern "C" int dpf_nndistance_strided_auto(int b, int n, const float *xyz, long 
 // here grid = (query tiles, j, 2 i + direction), every workgroup reads its two clouds in place, the per-point distances
 // are summed in the kernel and never written.  workspace: dpf_pairwise_cd_workspace_bytes(N1, N2, n, m) bytes.
 // Rows [i0, i1) only: what one rank of a row-sharded evaluation computes (cds still has N2 columns).
-// 512-query workgroups; 256-query ones for clouds of <= 256 points (half of a 16-wave workgroup would idle)
-static int pairwise_qw(int nmax) { return nmax <= 256 ? 8 : 16; }
+// (the workgroup's queries: dispatch.h's pairwise_qw)
 extern "C" size_t dpf_pairwise_cd_workspace_bytes(int n1, int n2, int n, int m) {
-    const int nmax = n > m ? n : m, per = pairwise_qw(nmax) * 32;
+    const int nmax = n > m ? n : m, per = dispatch::pairwise_qw(nmax) * 32;
     return (size_t)n1 * n2 * (2 * ((nmax + per - 1) / per) + 1) * sizeof(float);      // sums + one ticket per pair
 }
 extern "C" int dpf_pairwise_cd(int n1, int n2, int n, int m, const float *clouds1, const float *clouds2, float *cds,
@@ -798,7 +783,7 @@ extern "C" int dpf_pairwise_cd(int n1, int n2, int n, int m, const float *clouds
     MArgs ma;
     ma.d[0] = MDir{clouds1, clouds2, nullptr, nullptr, n, m, (long)n * 3, (long)m * 3};
     ma.d[1] = MDir{clouds2, clouds1, nullptr, nullptr, m, n, (long)m * 3, (long)n * 3};
-    const int nmax = n > m ? n : m, qw = pairwise_qw(nmax), nwg = (nmax + qw * 32 - 1) / (qw * 32);
+    const int nmax = n > m ? n : m, qw = dispatch::pairwise_qw(nmax), nwg = (nmax + qw * 32 - 1) / (qw * 32);
     const long npairs = (long)n1 * n2;
     hipStream_t s = (hipStream_t)stream;
     ma.pn2 = n2; ma.ticket = (unsigned *)workspace; ma.part = (float *)workspace + npairs; ma.cd = cds;
@@ -831,8 +816,6 @@ extern "C" size_t dpf_nndistance_cd_workspace_bytes(int b, int n, int m) {
     // sums (one per 64-query workgroup of nn_small_kernel, the finest tiling) + one ticket per cloud
     return (size_t)(b > 0 ? b : 0) * (2 * ((nmax + 63) / 64) + 1) * sizeof(float) + 16;
 }
-int nn_small_cd(int b, int n, const float *xyz, int m, const float *xyz2, float *result, int *result_i, float *result2,
-                int *result2_i, float *cd, void *workspace, int tickets_are_zero, hipStream_t s);      // chamfer.hip
 extern "C" int dpf_nndistance_cd(int b, int n, const float *xyz, int m, const float *xyz2, float *result, int *result_i,
                                  float *result2, int *result2_i, float *cd, void *workspace, size_t workspace_bytes,
                                  int tickets_are_zero, dpf_stream_t stream) {
@@ -840,21 +823,22 @@ extern "C" int dpf_nndistance_cd(int b, int n, const float *xyz, int m, const fl
     if (b == 0) return 0;
     if (!xyz || !xyz2 || !result || !result_i || !result2 || !result2_i || !cd) return DPF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    if (workspace && workspace_bytes >= dpf_nndistance_cd_workspace_bytes(b, n, m) && nnm_pays(b, n, m)) {
+    const dispatch::Switches sw = dispatch::snapshot();
+    const bool ws_ok = workspace && workspace_bytes >= dpf_nndistance_cd_workspace_bytes(b, n, m), pays = dispatch::nnm_pays(b, n, m, sw);
+    if (ws_ok && pays) {
         // tickets (first b words): zero on entry -- `tickets_are_zero` = 0 makes this call clear them first -- and zero again
         // on exit, so a caller that keeps the workspace pays the memset once
         if (!tickets_are_zero)
             if (hipError_t e = dpf_zero_async(workspace, (size_t)b * sizeof(unsigned), s); e != hipSuccess) return (int)e;
         // (the workgroup size is launch_nnm's choice: the scratch has room for the finest tiling's sums)
-        return launch_nnm(b, n, xyz, (long)n * 3, m, xyz2, (long)m * 3, result, result_i, result2, result2_i, s,
+        return launch_nnm(b, n, xyz, (long)n * 3, m, xyz2, (long)m * 3, result, result_i, result2, result2_i, sw, s,
                           (float *)workspace + b, false, (unsigned *)workspace, cd);
     }
-    if (workspace && workspace_bytes >= dpf_nndistance_cd_workspace_bytes(b, n, m) && !nnm_pays(b, n, m)) {
+    if (ws_ok) {
         // a rank's handful of clouds: the LDS-staged scan finishes the reduction the same way (chamfer.hip nn_small_kernel)
-        const int rc = nn_small_cd(b, n, xyz, m, xyz2, result, result_i, result2, result2_i, cd, workspace, tickets_are_zero, s);
+        const int rc = nn_small_cd(b, n, xyz, m, xyz2, result, result_i, result2, result2_i, cd, workspace, tickets_are_zero, sw, s);
         if (rc != DPF_ENOSUP) return rc;
     }
-    int rc = dpf_nndistance_auto(b, n, xyz, m, xyz2, result, result_i, result2, result2_i, stream);
-    if (rc) return rc;
+    if (int rc = nn_auto(b, n, xyz, (long)n * 3, m, xyz2, (long)m * 3, result, result_i, result2, result2_i, sw, s)) return rc;
     return dpf_chamfer_reduce(b, n, m, result, result2, cd, stream);
 }

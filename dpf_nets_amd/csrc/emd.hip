@@ -25,6 +25,7 @@
 
 #include <type_traits>
 
+#include "dispatch.h"
 #include "dpf_hip.h"
 #include "zero_fill.h"
 
@@ -32,7 +33,7 @@
 
 namespace {
 
-constexpr int MAXS = 16;   // max inner-loop slices (waves) per workgroup
+constexpr int MAXS = dispatch::EMD_MAXS;   // 16: max inner-loop slices (waves) per workgroup
 constexpr int NLEVEL = 9;  // annealing levels j = 7 .. -1 (approxmatch.cu:24)
 
 // Explicit fma / rn intrinsics: the read-modify-write and the deferred paths of approxmatch
@@ -199,7 +200,7 @@ __device__ __forceinline__ void stream_records(const u64 *__restrict__ C, int jb
     }
 }
 
-constexpr int PPW = 128;   // points per wave in the deferred kernels
+constexpr int PPW = dispatch::EMD_PPW;   // 128: points per wave in the deferred kernels
 
 // (xyz2, multiR) records for the first ratio pass
 // `gate`: the deferred path comes in two families -- these packed-VALU kernels (difference-form d^2, bit-identical to the
@@ -463,7 +464,7 @@ typedef unsigned u4 __attribute__((ext_vector_type(4)));
 
 constexpr int MT = 4;            // 32-point tiles per wave
 constexpr int MPW = 32 * MT;     // points per wave / workgroup
-constexpr int MSL = 8;           // max candidate slices (waves) per workgroup
+constexpr int MSL = dispatch::EMD_MSL;      // 8: max candidate slices (waves) per workgroup
 constexpr float EMD_MFMA_R2MAX = 16.f;    // log2(e) |x - c|^2 bound: g >= 7, T <= 0, the mixed terms' rounding <= 2e-4 at level 7
 constexpr float EMD_AMAX = 1000.f;        // bound of the integer parts (2 a and |a|^2 / 2048 stay 11-bit integers)
 constexpr int EMD_GMAX = 11;              // finest grid 2^-11: T >= -8
@@ -1315,16 +1316,6 @@ __global__ __launch_bounds__(64) void emd_mfma_debug_exponents_kernel(MfmaState 
     }
 }
 
-int pick_mfma_slices(int b, int npoints, int ninner) {
-    const long groups = (long)b * ((npoints + MPW - 1) / MPW);
-    const int tiles = (ninner + 31) / 32;
-    int s = 1;
-    while (s < MSL && groups * s < 4096 && tiles / (2 * s) >= 4) s *= 2;
-    return s;
-}
-
-bool g_matrix_path = true;
-
 
 // (xyz2_l, ratioR_level0..8[l]) records of 12 floats for the materialisation
 __global__ void emd_pack_levels_kernel(int n, int m, const float *__restrict__ xyz2, const float *__restrict__ ws,
@@ -1503,7 +1494,7 @@ __global__ __launch_bounds__(256) void emd_grad2_kernel(int n, int m, const floa
 //   group go through one recursive-halving butterfly (63 shuffles instead of 378), the four waves combine in
 //   LDS, and the workgroup's partial for those rows goes to part2[b][k-block][l][3]; emd_grad2_sum_kernel adds
 //   the k-blocks in a fixed order.
-constexpr int GROWS = 21;
+constexpr int GROWS = dispatch::EMD_GROWS;      // 21
 template <int K>
 __device__ __forceinline__ void halve_stage(float (&w)[32], int lane) {
     constexpr int n2 = 16 >> (K - 1);
@@ -1606,7 +1597,7 @@ __global__ __launch_bounds__(256) void emd_grad2_sum_kernel(int m, int nkb, cons
 // would have stored -- and goes into both gradients at once.  grad1: per-lane sums, the row slices combined in LDS in slice
 // order.  grad2: GROWS rows at a time through lane_sums64, as in emd_grad_fused_kernel; a wave's rows are its own, so its lane
 // sums are the column block's partials: part2[(cloud, column block, row)], added in block order by emd_grad2_recompute_sum_kernel.
-constexpr int GSL = 8;     // max row slices (waves) per workgroup: two waves per SIMD keep the 64 butterfly values in registers
+constexpr int GSL = dispatch::EMD_GSL;     // 8: max row slices (waves) per workgroup: two waves per SIMD keep the 64 butterfly values in registers
 __global__ __launch_bounds__(64 * GSL) void emd_materialize2_grad_kernel(int n, int m, LevelPairs lv, const unsigned *words,
                                                                          const float *__restrict__ xyz1, const float *__restrict__ rec,
                                                                          const float *__restrict__ ws, size_t lstride, size_t rstride,
@@ -1678,23 +1669,6 @@ __global__ __launch_bounds__(256) void emd_grad2_recompute_sum_kernel(int m, int
     float s = 0.f;
     for (int kb = 0; kb < nkb; ++kb) s += part2[((size_t)bi * nkb + kb) * rows * 3 + i];
     grad2[((size_t)bi * m + l) * 3 + c3] = s;
-}
-
-// inner-loop slices per workgroup so that the launch has >= ~2048 waves
-// slices for the approxmatch passes (both paths use the same ones, so their sums associate identically): enough
-// that the deferred kernels (128 points per wave) put ~4 waves on every SIMD
-int pick_match_slices(int b, int npoints, int ninner) {
-    const long groups = (long)b * ((npoints + PPW - 1) / PPW);
-    int s = 1;
-    while (s < MAXS && groups * s < 4096 && ninner / (2 * s) >= 64) s *= 2;
-    return s;
-}
-
-int pick_slices(int b, int npoints, int ninner) {
-    const long groups = (long)b * ((npoints + 63) / 64);
-    int s = 1;
-    while (s < MAXS && groups * s < 2048 && ninner / (2 * s) >= 64) s *= 2;
-    return s;
 }
 
 }  // namespace
@@ -1773,11 +1747,7 @@ static bool args_settle(int &rc, long b, int n, int m, bool pointers) {
 
 // 1 (default): the deferred path's passes run on the matrix cores when the coordinates allow it; 0: always the packed-VALU
 // kernels (bit-identical to the read-modify-write path).  Returns the previous setting.  Env DPF_EMD_MATRIX=0 sets the default.
-extern "C" int dpf_emd_set_matrix_path(int on) {
-    const int prev = g_matrix_path ? 1 : 0;
-    g_matrix_path = on != 0;
-    return prev;
-}
+extern "C" int dpf_emd_set_matrix_path(int on) { return dispatch::settable().emd_matrix.exchange(on != 0 ? 1 : 0); }
 
 // The levels' constants, for the passes and for whoever repeats the materialisation (dpf_matchcostgrad_recompute_ws).
 // level j's 4^(j-7) as fp16 powers of two (level_vectors): F down to 2^-14 (a normal fp16 number), f the rest, h = 2^(j-7)
@@ -1818,6 +1788,7 @@ struct PairCall { PairMap pm; unsigned *gates; int slice_b; };
 static int approxmatch_impl(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *temp, float *cost,
                             void *workspace, size_t workspace_bytes, dpf_stream_t stream, const PairCall *pc = nullptr,
                             bool keep_state = false) {
+    const dispatch::Switches sw = dispatch::snapshot();
     int rc;
     if (args_settle(rc, b, n, m, xyz1 && xyz2 && temp && (match || pc || keep_state))) return rc;
     const EmdLayout L = emd_layout(b, n, m, (uintptr_t)workspace);
@@ -1829,11 +1800,10 @@ static int approxmatch_impl(int b, int n, int m, const float *xyz1, const float 
     float multiL, multiR;
     if (n >= m) { multiL = 1; multiR = (float)(n / m); }   // integer division, approxmatch.cu:6-12
     else        { multiL = (float)(m / n); multiR = 1; }
-    static const bool env_matrix = [] { const char *e = getenv("DPF_EMD_MATRIX"); return !(e && e[0] == '0'); }();
-    const bool matrix = deferred && g_matrix_path && env_matrix;
+    const bool matrix = dispatch::emd_matrix_family(deferred, sw);
     unsigned *flag = matrix ? (pc ? pc->gates : ws_at<unsigned>(workspace, L.flag)) : nullptr;
     hipLaunchKernelGGL(emd_init_kernel, dim3((n + m + 255) / 256, b), dim3(256), 0, s, n, m, multiL, multiR, temp, flag, pm);
-    const int s1 = pick_match_slices(sb, n, m), s2 = pick_match_slices(sb, m, n);
+    const int s1 = dispatch::pick_match_slices(sb, n, m), s2 = dispatch::pick_match_slices(sb, m, n);
     const dim3 g1((n + 63) / 64, b), g2((m + 63) / 64, b);
     const dim3 h1((n + PPW - 1) / PPW, b), h2((m + PPW - 1) / PPW, b);               // deferred kernels: 128 points per wave
     // a ratio slot: a level's of the workspace, or (read-modify-write) the one behind remainL | remainR in every cloud's `temp`
@@ -1844,7 +1814,7 @@ static int approxmatch_impl(int b, int n, int m, const float *xyz1, const float 
     // The cost partials of a cloud pair: ONE region and stride for both families.  With a verdict per pair (dpf_pairwise_emd)
     // pairs of both families share a launch, and strides of their own -- (NP / 64) m1 and ceil(n / 128) s1, 128 and 64 at 2 048
     // points -- would lay one pair's partials over another's.
-    static_assert(MPW == PPW && MPW / (32 * MTM) * MSL <= MAXS, "matrix-core cost partials exceed the per-pair region");
+    static_assert(MPW == dispatch::EMD_MPW && MPW == PPW && MPW / (32 * MTM) * MSL <= MAXS, "matrix-core cost partials exceed the per-pair region");
     float *costpart = deferred ? ws_at<float>(workspace, L.costpart) : nullptr;
     const int cstride = L.cstride;
     // (the range check first: every kernel of either family looks at its verdict)
@@ -1867,7 +1837,7 @@ static int approxmatch_impl(int b, int n, int m, const float *xyz1, const float 
         int *l_s = ws_at<int>(workspace, L.ls);
         hipLaunchKernelGGL(emd_mfma_pack_kernel, dim3((NP + MP + 255) / 256, b), dim3(256), 0, s, st, multiR, xyz1, xyz2,
                            ws_at<const float>(workspace, L.meta), recA2_dense, ws, lstride);
-        const int m1 = pick_mfma_slices(sb, n, m), m2 = pick_mfma_slices(sb, m, n);
+        const int m1 = dispatch::pick_mfma_slices(sb, n, m), m2 = dispatch::pick_mfma_slices(sb, m, n);
         const dim3 q1(NP / MPW, b), q2(MP / MPW, b);
         int cur = 0, lj = 0;
         for (int j = 7; j > -2; --j, ++lj) {
@@ -2062,7 +2032,7 @@ extern "C" int dpf_matchcostgrad(int b, int n, int m, const float *xyz1, const f
     int rc;
     if (args_settle(rc, b, n, m, xyz1 && xyz2 && match && grad1 && grad2)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int s1 = pick_slices(b, n, m);
+    const int s1 = dispatch::pick_slices(b, n, m);
     hipLaunchKernelGGL(emd_grad1_kernel, dim3((n + 63) / 64, b), dim3(64, s1), 0, s, n, m, xyz1, xyz2, match, grad1);
     hipLaunchKernelGGL(emd_grad2_kernel, dim3((m + 3) / 4, b), dim3(256), 0, s, n, m, xyz1, xyz2, match, grad2);
     return (int)hipGetLastError();
@@ -2081,13 +2051,10 @@ extern "C" int dpf_matchcostgrad_ws(int b, int n, int m, const float *xyz1, cons
     int rc;
     if (args_settle(rc, b, n, m, xyz1 && xyz2 && match && grad1 && grad2)) return rc;
     const int nkb = (n + 255) / 256;
-    // one workgroup per 256 columns and cloud: with fewer than one per CU the row-parallel two-pass kernels win
-    // (measured r01, one pass vs two kernels: B=2, N=8192: 0.58 vs 0.29 ms; B=32, N=2048: 0.37 vs 0.30 ms;
-    // B=16, N=8192: 1.52 vs 2.26 ms)
-    if (!workspace || workspace_bytes < dpf_matchcostgrad_workspace_bytes(b, n, m) || (long)b * nkb < 512)
-        return dpf_matchcostgrad(b, n, m, xyz1, xyz2, match, grad1, grad2, stream);
+    const dispatch::GradForm form = dispatch::grad_form(b, n, m, workspace && workspace_bytes >= dpf_matchcostgrad_workspace_bytes(b, n, m));
+    if (form == dispatch::GradForm::TwoPass) return dpf_matchcostgrad(b, n, m, xyz1, xyz2, match, grad1, grad2, stream);
     hipStream_t s = (hipStream_t)stream;
-    if ((long)b * nkb < 1024 && m >= 4 * GROWS)     // fewer than four column-waves per SIMD: two row slices per workgroup
+    if (form == dispatch::GradForm::Fused2)
         hipLaunchKernelGGL(emd_grad_fused_kernel<2>, dim3(nkb, b), dim3(512), 0, s, n, m, xyz1, xyz2, match, grad1, (float *)workspace);
     else
         hipLaunchKernelGGL(emd_grad_fused_kernel<1>, dim3(nkb, b), dim3(256), 0, s, n, m, xyz1, xyz2, match, grad1, (float *)workspace);
@@ -2097,7 +2064,7 @@ extern "C" int dpf_matchcostgrad_ws(int b, int n, int m, const float *xyz1, cons
 
 // The gradients of dpf_matchcostgrad from the state dpf_approxmatch_costonly_ws left in its workspace: both families' kernels are
 // launched and the one that did not run in the forward returns at once (grad_gate_closed reads the saved verdict and setting --
-// never g_matrix_path).  scratch: the column blocks' grad2 partials, 12 bytes per (64-column block, row of the padded cloud 2):
+// never the process setting of the moment).  scratch: the column blocks' grad2 partials, 12 bytes per (64-column block, row of the padded cloud 2):
 // 3 / 16 n of the matching's size.  Reads the saved workspace only; allocates nothing, no synchronisation.
 extern "C" size_t dpf_matchcostgrad_recompute_workspace_bytes(int b, int n, int m) {
     if (b <= 0 || n <= 0 || m <= 0) return 0;
@@ -2118,7 +2085,7 @@ extern "C" int dpf_matchcostgrad_recompute_ws(int b, int n, int m, const float *
     float *part2 = (float *)scratch;
     {   // matrix-core family
         const MfmaState st = mfma_state(L, saved_workspace, b, n, m, nullptr, nullptr, PairMap{1, b, 0});
-        const int m1 = pick_mfma_slices(b, n, m), nkb = L.NP / (32 * MTM);
+        const int m1 = dispatch::pick_mfma_slices(b, n, m), nkb = L.NP / (32 * MTM);
         hipLaunchKernelGGL(emd_mfma_grad_kernel, dim3(nkb, b), dim3(64, m1), 0, s, st, level_scales(), words, xyz1, ws, L.lstride,
                            ws_at<const u4>(saved_workspace, L.recAs), ws_at<const float>(saved_workspace, L.rrs),
                            ws_at<const float>(saved_workspace, L.c2s), grad1, part2);
@@ -2126,9 +2093,7 @@ extern "C" int dpf_matchcostgrad_recompute_ws(int b, int n, int m, const float *
                            ws_at<const int>(saved_workspace, L.ls), (const float *)part2, grad2);
     }
     {   // packed-VALU family
-        const int nkb = (n + PPW - 1) / PPW;
-        int gs = 1;
-        while (gs < GSL && (long)b * nkb * gs < 2048 && m / (2 * gs) >= 2 * GROWS) gs *= 2;
+        const int nkb = (n + PPW - 1) / PPW, gs = dispatch::pick_grad_slices(b, n, m);
         hipLaunchKernelGGL(emd_materialize2_grad_kernel, dim3(nkb, b), dim3(64, gs), 0, s, n, m, level_pairs(), words, xyz1,
                            ws_at<const float>(saved_workspace, L.rec), ws, L.lstride, L.rstride, grad1, part2);
         hipLaunchKernelGGL(emd_grad2_recompute_sum_kernel<1>, dim3((m * 3 + 255) / 256, b), dim3(256), 0, s, m, m, nkb, words,

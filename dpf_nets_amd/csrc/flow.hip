@@ -1055,6 +1055,7 @@ static int flow_forward_impl(int n_layers, int B, int N, int mode, int precision
                              float flow_eps, dpf_stream_t stream, const float *base_mu, const long *mu_strides,
                              const float *base_lv, const long *lv_strides, float *z_out, double *xs_part = nullptr,
                              int xs_ka = 0, int xs_kb = -1, int *xs_rows = nullptr, bool packed16_ok = true) {
+    const dispatch::Switches sw = dispatch::snapshot();
     const int ns = ns_of(precision);
     if (!ns || n_layers <= 0 || B < 0 || N <= 0 || (mode != DPF_MODE_DIRECT && mode != DPF_MODE_INVERSE)) return DPF_EINVAL;
     if (B == 0) return 0;
@@ -1077,35 +1078,22 @@ static int flow_forward_impl(int n_layers, int B, int N, int mode, int precision
         a.lv_sb = lv_strides[0]; a.lv_sc = lv_strides[1]; a.lv_sn = lv_strides[2];
     }
     hipStream_t s = (hipStream_t)stream;
+    const dispatch::FlowForm form = dispatch::flow_form(n_layers, B, N, precision, xs_part != nullptr, packed16_ok, sw);
     // small batches (at most one 16-point tile per SIMD of the chip): the 16-point-tile kernel, csrc/flow16.hip
     a.packed16 = nullptr;
-    if (packed16_ok && flow16_serves(n_layers, B, N, precision, xs_part != nullptr)) {
+    if (form.kernel != dispatch::FlowKernel::Tile32) {
         a.packed16 = (const uint8_t *)packed + (size_t)n_layers * p_layer_bytes(ns);
-        return flow16_launch(&a, s);
+        return flow16_launch(&a, form, s);
     }
-    // 8-wave workgroups (256 points of one cloud) unless that leaves CUs without a workgroup
-    static const int force_fw = getenv("DPF_FLOW_WAVES") ? atoi(getenv("DPF_FLOW_WAVES")) : 0;
-    // waves (32-point tiles) per workgroup: as many as possible (each workgroup streams the layer
-    // weights through its own LDS) while the launch still has a workgroup for every CU
-    // (measured r01: below 4 waves the LDS-DMA fill of a layer, ~1.5 us for 38 KB on one CU, is no
-    // longer hidden, so 2- and 1-wave workgroups are only for clouds of <= 64 / <= 32 points)
-    int fw = force_fw;
-    if (!fw) {
-        fw = 8;
-        if ((long)B * ((N + 255) / 256) < 224) fw = 4;
-        if (N <= 64) fw = 2;
-        if (N <= 32) fw = 1;
+    if (xs_rows != nullptr) *xs_rows = form.xs_rows;
+    switch (form.fw * 10 + form.lpb) {                    // waves per workgroup, layers per LDS buffer (0: the skewed form)
+    case 80: return launch_flow_prec<8, 0>(precision, a, s);
+    case 82: return launch_flow_prec<8, 2>(precision, a, s);
+    case 81: return launch_flow_prec<8, 1>(precision, a, s);
+    case 41: return launch_flow_prec<4, 1>(precision, a, s);
+    case 21: return launch_flow_prec<2, 1>(precision, a, s);
+    default: return launch_flow_prec<1, 1>(precision, a, s);
     }
-    if (xs_rows != nullptr) *xs_rows = (N + TILE * (fw >= 8 ? 8 : fw >= 4 ? 4 : fw >= 2 ? 2 : 1) - 1) / (TILE * (fw >= 8 ? 8 : fw >= 4 ? 4 : fw >= 2 ? 2 : 1));
-    // two layers per LDS buffer where a CU gets one workgroup anyway and the 2 x 2 layers fit its LDS (two-part precisions)
-    static const int lpb_env = getenv("DPF_FLOW_LPB") ? atoi(getenv("DPF_FLOW_LPB")) : 0;
-    const bool pair_ok = ns <= 2 && n_layers >= 2 && lpb_env != 1 && (lpb_env == 2 || (long)B * ((N + 255) / 256) <= 256);
-    static const int skew_env = getenv("DPF_FLOW_SKEW") ? atoi(getenv("DPF_FLOW_SKEW")) : 1;
-    if (fw >= 8 && skew_env && ns <= 2) return launch_flow_prec<8, 0>(precision, a, s);
-    if (fw >= 8) return pair_ok ? launch_flow_prec<8, 2>(precision, a, s) : launch_flow_prec<8, 1>(precision, a, s);
-    if (fw >= 4) return launch_flow_prec<4, 1>(precision, a, s);
-    if (fw >= 2) return launch_flow_prec<2, 1>(precision, a, s);
-    return launch_flow_prec<1, 1>(precision, a, s);
 }
 
 extern "C" int dpf_flow_forward(int n_layers, int B, int N, int mode, int precision, const void *packed,

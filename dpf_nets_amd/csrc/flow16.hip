@@ -764,41 +764,18 @@ int launch16(const FlowArgs &a, hipStream_t s) {
 
 }  // namespace
 
-// 16-point tiles pay while they leave SIMDs a single wave: up to 1024 tiles (one per SIMD of the 256 CUs); f16x3 only; the
-// training forward's moment epilogue lives in the 32-point kernel.  DPF_FLOW_TILE16=0 / 1 forces the choice.
-static int g_tile16_mode = getenv("DPF_FLOW_TILE16") ? atoi(getenv("DPF_FLOW_TILE16")) : -1;
 // -1 (default): by size; 0: never; 1: whenever the precision allows (tests, tools/flow_sweep.py).  Returns the old mode.
-extern "C" int dpf_flow_set_tile16(int mode) {
-    const int old = g_tile16_mode;
-    g_tile16_mode = mode < 0 ? -1 : (mode ? 1 : 0);
-    return old;
-}
-bool flow16_serves(int n_layers, int B, int N, int precision, bool has_xs) {
-    const int env = g_tile16_mode;
-    if (precision != DPF_PREC_F16X3 || has_xs || env == 0 || n_layers > 128 || B > 65535) return false;
-    if (env == 1) return true;
-    return (long)B * ((N + 15) / 16) <= 1024;
-}
+extern "C" int dpf_flow_set_tile16(int mode) { return dispatch::set_mode(dispatch::settable().flow_tile16, mode); }
+// how many calls the 16-point kernel served
+extern "C" long dpf_flow_tile16_launches(void) { return dispatch::settable().tile16_launches.load(std::memory_order_relaxed); }
 
-static long g_tile16_launches = 0;
-extern "C" long dpf_flow_tile16_launches(void) { return g_tile16_launches; }   // how many calls the 16-point kernel served
-
-int flow16_launch(const void *flow_args, hipStream_t stream) {
+int flow16_launch(const void *flow_args, const dispatch::FlowForm &form, hipStream_t stream) {
     const FlowArgs &a = *(const FlowArgs *)flow_args;
-    ++g_tile16_launches;
-    static const int cw_env = getenv("DPF_FLOW16_CW") ? atoi(getenv("DPF_FLOW16_CW")) : 0;
-    // compute waves per workgroup (the loaders share their SIMDs): 4 = one per SIMD; 2 when that is what gives every CU a
-    // workgroup (8 + 4 waves would have to live in 168 registers each: the kernel spills there, so it is not built)
-    int cw = cw_env ? cw_env : 4;
-    if (!cw_env && (long)a.B * ((a.N + 63) / 64) < 160) cw = 2;
+    dispatch::settable().tile16_launches.fetch_add(1, std::memory_order_relaxed);
     const bool inv = a.mode == DPF_MODE_INVERSE;
-    // at most half a tile per SIMD: split every tile's two branches over two waves (DPF_FLOW16_SPLIT=0 / 1 forces)
-    static const int split_env = getenv("DPF_FLOW16_SPLIT") ? atoi(getenv("DPF_FLOW16_SPLIT")) : -1;
-    const bool split = split_env >= 0 ? split_env != 0 : (long)a.B * ((a.N + 15) / 16) <= 512;
-    if (split) {
+    if (form.kernel == dispatch::FlowKernel::Tile16Split)
         return inv ? launch16s<4, 4, true>(a, stream) : launch16s<4, 4, false>(a, stream);
-    }
-    if (cw >= 4) return inv ? launch16<4, 4, true>(a, stream) : launch16<4, 4, false>(a, stream);
+    if (form.cw >= 4) return inv ? launch16<4, 4, true>(a, stream) : launch16<4, 4, false>(a, stream);
     return inv ? launch16<2, 2, true>(a, stream) : launch16<2, 2, false>(a, stream);
 }
 

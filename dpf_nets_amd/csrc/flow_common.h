@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dispatch.h"
 #include "dpf_hip.h"
 #include "lds_attr.h"
 
@@ -211,9 +212,8 @@ inline int ns_of(int precision) {   // number of operand parts; DPF_PREC_F16X3 s
 int flow_forward_xstats(int B, int N, int mode, int precision, const void *packed, const int *meta, const float *film,
                         const float *p_in, float *ps, float *mus, float *logvars, float flow_eps, dpf_stream_t stream,
                         double *xs_part, int xs_ka, int xs_kb, int *xs_rows);
-// csrc-internal: defined in flow16.hip, called by flow.hip's dispatcher.  Returns a HIP error code, or -1000 when the
-// 16-point kernel does not serve the call (the caller then takes the 32-point kernel).
-int flow16_launch(const void *flow_args, hipStream_t stream);
-bool flow16_serves(int n_layers, int B, int N, int precision, bool has_xs);
+// csrc-internal: defined in flow16.hip, called by flow.hip's dispatcher with one of the two 16-point forms of dispatch.h's
+// flow_form.  Returns a HIP error code.
+int flow16_launch(const void *flow_args, const dispatch::FlowForm &form, hipStream_t stream);
 int flow16_pack(int n_layers, int G, const float *canon, void *packed16, hipStream_t s);
 #endif  // DPF_FLOW_COMMON_H

@@ -1134,7 +1134,7 @@ struct MeansJob {
     int nb;                      // rows (workgroups of pass 1) per cloud
     int rows;                    // rows of the grid taken by the role workgroups
 };
-constexpr int MJ_ROLES = (516 + 31) / 32;
+constexpr int MJ_ROLES = dispatch::TRAIN_MJ_ROLES;
 // total of column j of cloud b's rows, in row order, eight loads in flight
 __device__ __forceinline__ float cloud_col_total(const float *__restrict__ part1, int nb, int b, int j) {
     float s = 0.f;
@@ -1986,37 +1986,17 @@ extern "C" int dpf_train_kernel_times(int enable, double *us_out, long *calls_ou
     return 0;
 }
 
-// ---- the environment switches and the kernel forms they (or the measured thresholds) choose ---------------------------
-// Read once per process, at the first training call: DPF_TRAIN_SPLIT / DPF_TRAIN_ROLES (-1 = not set: the thresholds below
-// decide; 0 / 1 forces the form), DPF_TRAIN_FUSE_COLSUM (default 1) and the current device's CU count.
-struct TrainSwitches { int split, roles, fuse_colsum, n_cu; };
-struct TrainForm { bool split_h1, split1, split2, roles, fuse_colsum; };   // the forms of a layer's kernels at nblk ordinary workgroups per launch
+// The forms of a layer's kernels (dispatch.h's train_form: the thresholds and their measurements) for the process's environment
+// switches and the current device's CU count, both read once, at the first training call
+using dispatch::TrainForm;
 static TrainForm train_form(int ns, int nblk) {
-    static const TrainSwitches sw = [] {
-        auto env = [](const char *name, int unset) { return getenv(name) ? atoi(getenv(name)) : unset; };
+    static const int n_cu = [] {
         int dev = 0, n = 0;
         (void)hipGetDevice(&dev);
         (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return TrainSwitches{env("DPF_TRAIN_SPLIT", -1), env("DPF_TRAIN_ROLES", -1), env("DPF_TRAIN_FUSE_COLSUM", 1), n > 0 ? n : 256};
+        return n > 0 ? n : 256;
     }();
-    const bool forced = sw.split >= 0, on = sw.split != 0;
-    TrainForm f;
-    // small batches: the two conditioner branches in two workgroups each (at most half a workgroup per CU otherwise).  r04,
-    // B = 8: tstats_h1 9.5 -> 8.7 us; at 128 workgroups -- B = 16 -- the statistics and pass 1 are better off unsplit (tbwd1
-    // 15.7 us unsplit, 18.1 split), only pass 2 gains
-    f.split_h1 = f.split1 = forced ? on : nblk <= 64;
-    // (bf16x6's three forward parts do not leave the one-branch-per-wave form its registers: that precision keeps one branch per workgroup)
-    f.split2 = ns == 3 || (forced ? on : nblk <= 128);
-    // Who finishes pass 1 -- per-cloud totals, FiLM gradients, dW2 / db2, the BN1-backward means?  Pass 2 needs a CU per workgroup
-    // (158 KB of LDS): role workgroups at the front of its grid (MeansJob) cost nothing where CUs are idle and a whole round of
-    // late workgroups where they are not.  So: roles while the ordinary workgroups + MJ_ROLES fit the chip's CUs, else pass 1's
-    // per-cloud ticket and a recomputation of the means by every workgroup of pass 2 (r02-r04).  DPF_TRAIN_ROLES=0/1 forces either.
-    // (the role form is built for the one-branch-per-workgroup kernel only: that is the form small batches run)
-    f.roles = f.split2 && (sw.roles >= 0 ? sw.roles != 0 : 2 * nblk + MJ_ROLES <= sw.n_cu);
-    // r04: the column sums of the layer above's pass-2 partials ride in pass 1's launch (ColsumJob) instead of a tcolsum launch
-    // of their own between the two layers; DPF_TRAIN_FUSE_COLSUM=0 keeps the separate launch
-    f.fuse_colsum = sw.fuse_colsum != 0;
-    return f;
+    return dispatch::train_form(ns, nblk, n_cu, dispatch::env_switches());
 }
 
 // What the layers of one stack call share, forward or backward: the checked sizes, the floats per layer of the (L, ...)

@@ -14,6 +14,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "dispatch.h"
+
 #pragma clang fp contract(off)
 
 namespace {
@@ -50,4 +52,11 @@ __device__ __forceinline__ bool nn_query_far(float x, float y, float z) {
 }
 
 }  // namespace
+
+// csrc-internal, defined in chamfer.hip and also called by chamfer_mfma.hip's entries, with the switches the entry read at its
+// top: dpf_nndistance_strided itself, and dpf_nndistance_cd's fast path where the LDS-staged scan serves (else DPF_ENOSUP)
+int nn_scan_strided(int b, int n, const float *xyz, long xyz_stride, int m, const float *xyz2, long xyz2_stride, float *result,
+                    int *result_i, float *result2, int *result2_i, const dispatch::Switches &sw, hipStream_t s);
+int nn_small_cd(int b, int n, const float *xyz, int m, const float *xyz2, float *result, int *result_i, float *result2,
+                int *result2_i, float *cd, void *workspace, int tickets_are_zero, const dispatch::Switches &sw, hipStream_t s);
 #endif

@@ -53,7 +53,8 @@ int dpf_nndistance(int b, int n, const float *xyz, int m, const float *xyz2,
 
 /* Which kernel serves dpf_nndistance(_strided) for rank-sized batches of 1024..8192-point clouds (< 512 waves of the scan):
  * the LDS-staged one-query-per-lane kernel (csrc/chamfer.hip nn_small_kernel, r04) or the scalar-load scan.  Same bits.
- * mode: -1 = by size (default; env DPF_NN_SMALL), 0 = never, 1 = whenever the clouds fit.  Returns the previous mode. */
+ * mode: -1 = by size (default; env DPF_NN_SMALL), 0 = never, 1 = whenever the clouds fit.  Returns the previous mode.
+ * Sets an atomic process default; meant for tests and tools.  A call in flight keeps the value it read at entry. */
 int dpf_nn_small_mode(int mode);
 
 /* dpf_nndistance with explicit strides (in floats) between consecutive clouds of
@@ -120,7 +121,8 @@ size_t dpf_approxmatch_workspace_bytes(int b, int n, int m);
  * MFMAs (tools/ubench/pk_vs_mfma_forms.hip).  The Makefile refuses to link ANY object that holds that form, or packed
  * fp32 beside MFMAs, or an emd.o whose MFMAs do not have the properties of the build that repeats (tools/mfma_overlap_check.py);
  * tests/test_gpu_emd.py holds the repeat tests, tests/test_gpu_interference.py runs the kernels beside an MFMA-issuing kernel of
- * another stream.  Returns the previous setting. */
+ * another stream.  Returns the previous setting.  Sets an atomic process default (ANDed with env DPF_EMD_MATRIX, which the
+ * setter cannot override); meant for tests and tools.  A call in flight keeps the value it read at entry. */
 int dpf_emd_set_matrix_path(int on);
 int dpf_approxmatch_ws(int b, int n, int m, const float *xyz1, const float *xyz2,
                        float *match, float *temp, void *workspace, size_t workspace_bytes,
@@ -322,7 +324,8 @@ int dpf_flow_forward_base(int n_layers, int B, int N, int precision, const void 
  * a wave owns 32 points (v_mfma_f32_32x32x16, csrc/flow.hip) or, for small per-GPU batches at f16x3 -- at most one tile per
  * SIMD of the chip, B * ceil(N / 16) <= 1024, e.g. the 4 clouds a rank of an 8-GPU job holds of BASELINE's 32 -- 16 points
  * (v_mfma_f32_16x16x32, csrc/flow16.hip).  mode: -1 = by size (default; env DPF_FLOW_TILE16), 0 = never, 1 = whenever
- * the precision allows.  Returns the previous mode.  Process-wide; meant for tests and measurements. */
+ * the precision allows.  Returns the previous mode.  Sets an atomic process default; meant for tests and tools.  A call in
+ * flight keeps the value it read at entry. */
 int dpf_flow_set_tile16(int mode);
 long dpf_flow_tile16_launches(void);   /* calls of dpf_flow_forward / _base served by the 16-point kernel so far */
 
