@@ -27,11 +27,13 @@
 // fragment (0.5 VALU op per pair).  Since r04 the sweep keeps no queue: a chunk of
 // 32 tiles leaves its surrogate minima in registers, then every tile within tau of
 // the minimum SO FAR is marked in a per-lane bit mask -- the final minimum can only
-// be lower, so the marked tiles are a superset of what the final threshold selects
-// -- and only those few tiles are evaluated with the exact formula and the
-// (d, index) lexicographic rule, 64 at a time from one wave-wide work list (a lane
-// has 1-2 of them, the wave's maximum is ~4: the per-lane loop of r01-r03 paid a
-// whole evaluation per lane and round).  A chunk that is full of genuine near-ties
+// be lower, so the marked tiles are a superset of what the final threshold selects.
+// Since r10 a pass of 64 tiles (two chunks) is evaluated ONCE: the first chunk's mask
+// waits, is dropped where the lane's minimum of it lies above the pass's final
+// threshold, and only the tiles left in both masks are evaluated with the exact
+// formula and the (d, index) lexicographic rule, 64 at a time from one wave-wide work
+// list (a lane has 1-2 of them, the wave's maximum is ~4: the per-lane loop of r01-r03
+// paid a whole evaluation per lane and round).  A pass that is full of genuine near-ties
 // (duplicate points, lattice data: more than 256 items per wave) keeps the per-lane
 // loop, so the result is exact for any finite input and the cost degrades gracefully.
 // The surrogate works on coordinates translated to the mean of the first 64
@@ -63,7 +65,7 @@ constexpr int CT = dispatch::NNM_CT;           // candidate tiles resident in LD
 // structure-of-arrays form makes a lane's 16 candidates 12 quad reads instead of 16.
 constexpr int PROW = 100;        // floats
 constexpr int SCH = 32;          // tiles per sweep chunk: their surrogate minima stay in registers until the chunk's threshold is known
-constexpr int WCAP = SCH * 64 / 8;   // work items of a wave per chunk: their 8-byte results reuse the survivor lists' 2 KiB
+constexpr int WCAP = SCH * 64 / 8;   // work items of a wave per pass: their 8-byte results reuse the survivor lists' 2 KiB
 constexpr int NNM_PTS = CT * 1024, NNM_LISTS = NNM_PTS + CT * PROW * 4;       // byte offsets: fragments | points | survivor lists / results | work lists
 __host__ __device__ constexpr int nnm_lds_bytes(int qw) { return NNM_LISTS + qw * SCH * 64 + qw * WCAP * 2; }
 
@@ -443,9 +445,23 @@ __global__ __launch_bounds__(QW * 64) void nnm_kernel(MArgs args) {
             // registers, near-ties in LDS, an overflow path): ~13 VALU + two exec-mask branches per tile beside the 10 of the
             // v_min3 tree, and with 64 lanes some lane hits in almost every tile -- ~94 cycles per tile against the MFMA's 32.
             // Now a chunk of SCH tiles leaves only its surrogate minima in registers (MFMAs issued one group ahead of the trees
-            // that read them: no wait states), then the threshold is known -- running minimum so far + tau: the final one can
+            // that read them: no wait states), then a threshold is known -- running minimum so far + tau: the final one can
             // only be lower, so the survivors are a superset -- and a branch-free pass marks the lane's survivors in a bit mask
-            // (compare, shift-or); they are evaluated exactly, from a wave-wide work list (below).
+            // (compare, shift-or).
+            // r10: sweep, mark, THEN evaluate -- once per pass, not once per chunk.  A pass is at most two chunks (CT = 2 SCH).
+            // The first one is only swept and marked: its mask (against the threshold of its time) and the lane's minimum of
+            // it wait in two registers.  The last chunk of the pass is marked against the pass's FINAL threshold (the minimum
+            // over both lane halves, every chunk of this pass and every earlier pass, + tau), and the waiting chunk is dropped
+            // whole where the lane's minimum of it lies above that threshold: none of its tiles can then pass the same compare.
+            // Evaluated per chunk, the chunk that does NOT hold a query's neighbour still sent its own best tile into a round
+            // of its own (the threshold could not know the other chunk yet): ~1.1 half-empty rounds per chunk, now ~1 per
+            // pass.  The bits cannot change: a dropped tile has s > s_min + tau, and every exact minimiser and every exact tie
+            // has s <= s_min + 2E < s_min + tau (header); what is kept is still a superset of what the final threshold
+            // selects, and the owners' (d, index) merge does not care about order.
+            static_assert(CT <= 2 * SCH, "one chunk waits in registers: a pass is at most two chunks");
+            static_assert(CT <= 256, "a work item names its tile of the pass in eight bits");
+            unsigned dmask = 0, smask = 0;                // survivors: the waiting chunk's, the last chunk's
+            float dcm = 0.f, thr = 0.f;                   // the lane's minimum of the waiting chunk; the threshold of the last mark
             for (int c0 = 0; c0 < tn; c0 += SCH) {
                 const int cn = min(SCH, tn - c0);                             // wave-uniform
                 float mt[SCH];
@@ -504,18 +520,18 @@ __global__ __launch_bounds__(QW * 64) void nnm_kernel(MArgs args) {
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
-                DPF_T(4 + 5 * (c0 / SCH))
+                DPF_T(4 + 2 * (c0 / SCH))
                 float cm = fminf(fminf(mt[0], mt[1]), mt[2]);
 #pragma unroll
                 for (int u = 3; u + 1 < SCH; u += 2) cm = fminf(fminf(cm, mt[u]), mt[u + 1]);
                 cm = fminf(cm, mt[SCH - 1]);
                 smin = fminf(smin, cm);
-                const float thr = fminf(smin, __shfl_xor(smin, 32)) + tau;
+                thr = fminf(smin, __shfl_xor(smin, 32)) + tau;
                 // the lane's survivors as a bit mask (tile u at bit SCH - 1 - u): a compare and a shift-or per tile, no list
                 // smask = 2 smask + (mt[u] <= thr) per tile: a compare and an add-with-carry (the compiler's own form is compare,
                 // select, shift, or).  Sixteen tiles per asm statement (the operand limit is 30): one statement per tile had the
                 // compiler put a wait state between every two of them
-                unsigned smask = 0;
+                smask = 0;
                 static_assert(SCH == 32, "the mask is built sixteen tiles at a time, twice");
 #define NNM_MK(n) "v_cmp_le_f32 vcc, %" #n ", %17\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
 #pragma unroll
@@ -530,65 +546,84 @@ __global__ __launch_bounds__(QW * 64) void nnm_kernel(MArgs args) {
 #undef NNM_MK
                 // (a ragged last chunk repeated its last tile in slots cn .. SCH - 1: those bits name tiles that are not there)
                 if (cn < SCH) smask &= ~0u << (SCH - cn);
-                const int nsurv = __builtin_popcount(smask);
-                DPF_T(5 + 5 * (c0 / SCH))
-                // Exact evaluation.  A lane has 1-2 survivors per chunk on average but the wave's maximum is ~4, and a
-                // round of the per-lane loop costs a whole exact_tile for every lane: instead the wave's survivors go into
-                // ONE lane-major work list (exclusive scan of the counts), 64 items are evaluated per round by whichever
-                // lane comes -- the owner's query arrives by shuffle -- and the owners merge their own results under the
-                // (d, index) rule, which does not care about order.  (An adversarial chunk with more than WCAP items keeps
-                // the per-lane loop.)  The scan is six DPP additions; the list is written and merged for as many rounds as SOME
-                // lane has survivors (a ballot per round: no wave-wide maximum is taken for it).
-                int off = (int)wave_scan_add((unsigned)nsurv);
-                const int W = __builtin_amdgcn_readlane(off, 63);
-                off -= nsurv;
-                if (W <= WCAP) {
-                    {
-                        unsigned mk = smask;
-                        for (int e = 0; __builtin_amdgcn_ballot_w64(mk != 0) != 0; ++e) {
-                            if (mk != 0) wl[off + e] = (unsigned short)((lane << 8) | (SCH - 1 - __builtin_ctz(mk)));
-                            mk &= mk - 1;
-                        }
+                DPF_T(5 + 2 * (c0 / SCH))
+                if (c0 + SCH < tn) { dmask = smask; dcm = cm; }              // (wave-uniform) not the last chunk: it waits
+            }
+            // thr is the pass's final threshold now.  The waiting chunk stays only where the lane's minimum of it reaches it.
+#ifdef DPF_PROFILE
+            const unsigned dmask_all = dmask;
+#endif
+            dmask = dcm <= thr ? dmask : 0u;
+            const int lb = (tn > SCH ? SCH : 0) + SCH - 1;                    // the last chunk's tile u of the pass is lb - bit
+            const int n0 = __builtin_popcount(dmask), nsurv = n0 + __builtin_popcount(smask);
+            // Exact evaluation.  A lane has 1-2 survivors per pass on average but the wave's maximum is ~4, and a
+            // round of the per-lane loop costs a whole exact_tile for every lane: instead the wave's survivors go into
+            // ONE lane-major work list (exclusive scan of the counts; a lane's items of the waiting chunk, then those of the
+            // last one), 64 items are evaluated per round by whichever lane comes -- the owner's query arrives by shuffle --
+            // and the owners merge their own results under the (d, index) rule, which does not care about order.  (An
+            // adversarial pass with more than WCAP items keeps the per-lane loop.)  The scan is six DPP additions; the list is
+            // written -- one item of either chunk per round -- and merged for as many rounds as SOME lane has survivors (a
+            // ballot per round: no wave-wide maximum is taken for it).
+            int off = (int)wave_scan_add((unsigned)nsurv);
+            const int W = __builtin_amdgcn_readlane(off, 63);
+            off -= nsurv;
+#ifdef DPF_PROFILE
+            // rounds of this pass, the rounds the per-chunk evaluation had made of the same masks, and the items
+            if (prof_at != nullptr) {
+                const int w0 = __builtin_amdgcn_readlane((int)wave_scan_add((unsigned)__builtin_popcount(dmask_all)), 63);
+                const int w1 = __builtin_amdgcn_readlane((int)wave_scan_add((unsigned)__builtin_popcount(smask)), 63);
+                if (lane == 0) { prof_at[11] = (W + 63) / 64; prof_at[12] = (w0 + 63) / 64 + (w1 + 63) / 64; prof_at[13] = W; }
+            }
+#endif
+            if (W <= WCAP) {
+                {
+                    unsigned mk0 = dmask, mk1 = smask;
+                    for (int e = 0; __builtin_amdgcn_ballot_w64((mk0 | mk1) != 0) != 0; ++e) {
+                        if (mk0 != 0) wl[off + e] = (unsigned short)((lane << 8) | (SCH - 1 - __builtin_ctz(mk0)));
+                        if (mk1 != 0) wl[off + n0 + e] = (unsigned short)((lane << 8) | (lb - __builtin_ctz(mk1)));
+                        mk0 &= mk0 - 1;
+                        mk1 &= mk1 - 1;
                     }
-                    DPF_T(6 + 5 * (c0 / SCH))
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    for (int i0 = 0; i0 < W; i0 += 64) {
-                        const int i = i0 + lane;
-                        const unsigned item = wl[min(i, W - 1)];
-                        const int sl = (int)(item >> 8), tl = c0 + (int)(item & 255u);
-                        const float sx = __shfl(qx, sl), sy = __shfl(qy, sl), sz = __shfl(qz, sl);
-                        float m; int k;
-                        exact_tile_mk(spts, nc, t0 + tl, tl, sl >> 5, sx, sy, sz, m, k);
-                        if (i < W) res[i] = make_uint2(__float_as_uint(m), (unsigned)k);
+                }
+                DPF_T(8)
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                for (int i0 = 0; i0 < W; i0 += 64) {
+                    const int i = i0 + lane;
+                    const unsigned item = wl[min(i, W - 1)];
+                    const int sl = (int)(item >> 8), tl = (int)(item & 255u);
+                    const float sx = __shfl(qx, sl), sy = __shfl(qy, sl), sz = __shfl(qz, sl);
+                    float m; int k;
+                    exact_tile_mk(spts, nc, t0 + tl, tl, sl >> 5, sx, sy, sz, m, k);
+                    if (i < W) res[i] = make_uint2(__float_as_uint(m), (unsigned)k);
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                DPF_T(9)
+                for (int e = 0; __builtin_amdgcn_ballot_w64(e < nsurv) != 0; ++e) {
+                    if (e < nsurv) {
+                        const uint2 r = res[off + e];
+                        const float m = __uint_as_float(r.x);
+                        const int k = (int)r.y;
+                        const bool better = k != INT_MAX && (m < best || (m == best && k < bidx));
+                        best = better ? m : best;
+                        bidx = better ? k : bidx;
                     }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    DPF_T(7 + 5 * (c0 / SCH))
-                    for (int e = 0; __builtin_amdgcn_ballot_w64(e < nsurv) != 0; ++e) {
-                        if (e < nsurv) {
-                            const uint2 r = res[off + e];
-                            const float m = __uint_as_float(r.x);
-                            const int k = (int)r.y;
-                            const bool better = k != INT_MAX && (m < best || (m == best && k < bidx));
-                            best = better ? m : best;
-                            bidx = better ? k : bidx;
-                        }
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();                      // the results' space is the next chunk's
-                    DPF_T(8 + 5 * (c0 / SCH))
-                } else {
-                    const int smax = (int)wave_max_u32((unsigned)nsurv);
-                    unsigned mk = smask;
-                    for (int e = 0; e < smax; ++e) {
-                        const bool take = mk != 0;
-                        const int tl = c0 + (take ? SCH - 1 - __builtin_ctz(mk) : 0);
-                        mk &= mk - 1;
-                        float b2 = best; int i2 = bidx;
-                        exact_tile(spts, nc, t0 + tl, tl, h, qx, qy, qz, b2, i2);
-                        if (take) { best = b2; bidx = i2; }
-                    }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();                          // the results' space is the next pass's
+                DPF_T(10)
+            } else {
+                const int smax = (int)wave_max_u32((unsigned)nsurv);
+                unsigned mk0 = dmask, mk1 = smask;
+                for (int e = 0; e < smax; ++e) {
+                    const bool first = mk0 != 0, take = (mk0 | mk1) != 0;
+                    const int tl = first ? SCH - 1 - __builtin_ctz(mk0) : mk1 != 0 ? lb - __builtin_ctz(mk1) : 0;
+                    mk1 = first ? mk1 : mk1 & (mk1 - 1);
+                    mk0 &= mk0 - 1;
+                    float b2 = best; int i2 = bidx;
+                    exact_tile(spts, nc, t0 + tl, tl, h, qx, qy, qz, b2, i2);
+                    if (take) { best = b2; bidx = i2; }
                 }
             }
         }

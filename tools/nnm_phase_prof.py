@@ -16,9 +16,13 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-PHASES = ["entry -> mu, query R2 known", "fragment build (pass 0)", "R2 reduce, barrier, tau", "chunk 0: sweep", "chunk 0: minimum, threshold, mask",
-          "chunk 0: scan, work list", "chunk 0: evaluation rounds", "chunk 0: owners merge", "chunk 1: sweep", "chunk 1: minimum, threshold, mask",
-          "chunk 1: scan, work list", "chunk 1: evaluation rounds", "chunk 1: owners merge", "half merge, stores", "sum, barrier, ticket, CD finish"]
+# stamp k of a wave -> stamp k + 1, except where slots hold counters: 11 = evaluation rounds of the pass, 12 = the rounds the
+# per-chunk evaluation (before r10) had made of the same masks, 13 = work items of the pass
+PHASES = [(0, 1, "entry -> mu, query R2 known"), (1, 2, "fragment build (pass 0)"), (2, 3, "R2 reduce, barrier, tau"),
+          (3, 4, "chunk 0: sweep"), (4, 5, "chunk 0: minimum, threshold, mask"), (5, 6, "chunk 1: sweep"),
+          (6, 7, "chunk 1: minimum, final threshold, mask"), (7, 8, "pass: prune, scan, work list"), (8, 9, "pass: evaluation rounds"),
+          (9, 10, "pass: owners merge"), (10, 14, "half merge, stores"), (14, 15, "sum, barrier, ticket, CD finish")]
+STAMPS = [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 14, 15]
 
 
 def classify(op):
@@ -113,9 +117,10 @@ CLASSES = ("VALU", "MFMA", "LDS", "SALU", "VMEM", "wait")
 
 def print_blocks(path, rounds):
     """The three blocks a wave spends its issues in at the headline shape, found by what they hold -- the full-chunk sweep (32
-    MFMAs and the fewest SALU: immediate offsets), the chunk's minimum + mask + scan (the add-with-carry chain), a work-list
-    evaluation round (ds_read_b128 of points + the owners' queries by ds_bpermute) -- and their sum per wave and pass:
-    2 chunks x (sweep + mask) + `rounds` x round.  Prologue, build, list loops and epilogue are not in the sum."""
+    MFMAs and the fewest SALU: immediate offsets), the chunk's minimum + mask (the add-with-carry chain; before r10 the block also
+    held the chunk's scan, which now stands once per pass behind the loop), a work-list evaluation round (ds_read_b128 of points +
+    the owners' queries by ds_bpermute) -- and their sum per wave and pass: 2 chunks x (sweep + mask) + `rounds` x round.
+    Prologue, build, prune + scan, list loops and epilogue are not in the sum."""
     bl = block_account(path)
     sweep = min((b for b in bl if b[1].get("MFMA", 0) == 32), key=lambda b: b[1].get("SALU", 0))
     mask = max(bl, key=lambda b: sum(1 for op in b[2] if op.startswith("v_addc_co")))
@@ -124,7 +129,7 @@ def print_blocks(path, rounds):
     print("hot blocks of %s (unstamped listing), issues per execution: %s" % (os.path.basename(path), meta(path)))
     print("  %-28s %6s  %s" % ("block", "all", "  ".join("%5s" % c for c in CLASSES)))
     tot = dict.fromkeys(CLASSES, 0.0)
-    for name, b, k in (("full-chunk sweep (32 tiles)", sweep, 2), ("minimum + mask + scan", mask, 2), ("evaluation round (64 items)", rnd, rounds)):
+    for name, b, k in (("full-chunk sweep (32 tiles)", sweep, 2), ("minimum + mask", mask, 2), ("evaluation round (64 items)", rnd, rounds)):
         print("  %-28s %6d  %s   x %g   [%s]" % (name, sum(b[1].values()), "  ".join("%5d" % b[1].get(c, 0) for c in CLASSES), k, b[0]))
         for c in CLASSES:
             tot[c] += k * b[1].get(c, 0)
@@ -137,7 +142,7 @@ def main():
     ap.add_argument("--asm", default=os.path.join(ROOT, "dpf_nets_amd", "csrc", "chamfer_mfma_prof.s"))
     ap.add_argument("--asm-only", action="store_true")
     ap.add_argument("--blocks", metavar="LISTING", help="hot-block issue counts of an UNSTAMPED chamfer_mfma.s, then exit")
-    ap.add_argument("--rounds", type=float, default=2.2, help="evaluation rounds per wave and pass (measured at the headline shape)")
+    ap.add_argument("--rounds", type=float, default=1.2, help="evaluation rounds per wave and pass (measured at the headline shape: the account's last lines; 2.2 before r10)")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--points", type=int, default=2048)
     a = ap.parse_args()
@@ -180,13 +185,12 @@ def main():
         torch.cuda.synchronize()
         h.dpf_debug_set_nnm_prof(None)
         runs.append(prof.cpu().numpy().astype(np.int64).reshape(-1, 16))
-    t = np.stack(runs)                                   # (runs, 128 waves, 16 stamps)
-    assert (t > 0).all(), "a stamp is missing: is this the headline shape (two chunks, one pass)?"
-    d = np.diff(t, axis=2)
+    t = np.stack(runs)                                   # (runs, 128 waves, 16 slots)
+    assert (t[:, :, STAMPS] > 0).all(), "a stamp is missing: is this the headline shape (two chunks, one pass, a list within its capacity)?"
     print("library %s: B = %d, n = m = %d; shader cycles (s_memtime) per phase over %d runs x %d waves" % (os.path.basename(a.lib), B, n, t.shape[0], t.shape[1]))
     print("  %-38s %8s %8s %8s %8s" % ("phase", "median", "p10", "p90", "max"))
-    for k, name in enumerate(PHASES):
-        v = d[:, :, k].ravel()
+    for k0, k1, name in PHASES:
+        v = (t[:, :, k1] - t[:, :, k0]).ravel()
         print("  %-38s %8.0f %8.0f %8.0f %8.0f" % (name, np.median(v), np.percentile(v, 10), np.percentile(v, 90), v.max()))
     tot = (t[:, :, 15] - t[:, :, 0]).ravel()
     print("  %-38s %8.0f %8.0f %8.0f %8.0f" % ("entry -> end, per wave", np.median(tot), np.percentile(tot, 10), np.percentile(tot, 90), tot.max()))
@@ -195,6 +199,9 @@ def main():
     print("  %-38s %8.0f %8.0f %8.0f %8.0f" % ("first entry -> last end, per workgroup", np.median(span), np.percentile(span, 10), np.percentile(span, 90), span.max()))
     tail = (wg[:, :, 0, 15] - wg[:, :, :, 14].max(axis=2)).ravel()
     print("  %-38s %8.0f %8.0f %8.0f %8.0f" % ("last wave's stores -> wave 0's end", np.median(tail), np.percentile(tail, 10), np.percentile(tail, 90), tail.max()))
+    print("  per wave and pass (mean, min .. max): evaluation rounds %.2f (%d .. %d); evaluated per chunk the same masks gave %.2f (%d .. %d); "
+          "work items %.1f (%d .. %d)" % (t[:, :, 11].mean(), t[:, :, 11].min(), t[:, :, 11].max(), t[:, :, 12].mean(), t[:, :, 12].min(),
+                                          t[:, :, 12].max(), t[:, :, 13].mean(), t[:, :, 13].min(), t[:, :, 13].max()))
 
 
 if __name__ == "__main__":
