@@ -2,16 +2,17 @@
 (lib/networks/decoders.py:41-72): forward(p, g, mode) -> (ps, mus, logvars), three
 list-likes of 3*n_flows (B,3,N) tensors in DIRECT order for both modes.
 
-Eval mode runs ALL layers in one fused HIP launch (csrc/flow.hip); the lists are
-FlowLists over three (L,B,3,N) buffers the kernel fills.  Training mode on CUDA
-tensors runs the HIP training kernels for the whole stack as one autograd node
-(networks/train_engine.py); `forward_torch` chains the layers' tensor-op path
-(decoders.py:58-70) for CPU tensors / DPF_TRAIN_IMPL=torch."""
+The whole stack is ONE fused launch (FlowLists over three (L,B,3,N) buffers the kernel fills), one training node or one
+frozen-statistics node; `forward_torch` chains the layers' tensor-op path (decoders.py:58-70).  Who serves a call:
+networks/backend.py (point_flow, sample_and_decode)."""
+import torch
 import torch.nn as nn
 
-from .flows import CondRealNVPFlow3DTriple, EvalAutograd, _needs_autograd, use_hip_training, train_stack, stack_spec, frozen_stack
+from . import backend as B
+from .backend import Backend
+from .flows import CondRealNVPFlow3DTriple, EvalAutograd, choose, train_stack, stack_spec, cuda_fp32, run_frozen_stack
 from .flowlist import FlowList
-from .layers import PackedWeights, wants_frozen_hip
+from .layers import PackedWeights, warn_eval_autograd
 from .engine import FlowStack
 
 
@@ -30,6 +31,13 @@ class LocalCondRNVPDecoder(EvalAutograd, PackedWeights, nn.Module):
     def coupling_layers(self):
         """All 3*n_flows CondRealNVPFlow3D modules in DIRECT order."""
         return [lyr for tri in self.flows for lyr in tri.layers()]
+
+    def _layers(self, n_layers):
+        layers = self.coupling_layers()
+        return layers if n_layers is None else layers[:int(n_layers)]
+
+    def _all_params(self):
+        return stack_spec(self, self.coupling_layers()).all_params()
 
     def stack(self):
         return self.packed_stack(lambda: FlowStack(self.coupling_layers()))
@@ -70,19 +78,21 @@ class LocalCondRNVPDecoder(EvalAutograd, PackedWeights, nn.Module):
         place; `noise` defaults to torch.randn_like(logvar0) -- drawn by torch, so the generator stream is the caller's.
         In eval mode on CUDA the sample is formed in the fused kernel's prologue (no exp / mul / add launches, no
         materialised z round trip); otherwise this is exactly the two reference calls."""
-        import torch
         if noise is None:
             noise = torch.randn_like(logvar0)                                      # models.py:78
-        if self.eval_autograd == "hip":
-            from .frozen_engine import cuda_fp32
-            if wants_frozen_hip(self, stack_spec(self, self.coupling_layers()).all_params, noise, mu0, logvar0, g) and \
-                    cuda_fp32(noise, mu0, logvar0, g):
-                # the gradient must reach mu0 / logvar0 / noise: z by tensor ops in front of the node
-                z = noise * torch.exp(0.5 * logvar0) + mu0
-                return (z,) + tuple(self.forward(z, g, mode="direct"))
-        fused = (not self.training and noise.is_cuda and not _needs_autograd(noise, mu0, logvar0, g)
-                 and noise.dtype == torch.float32 and mu0.dtype == torch.float32 and logvar0.dtype == torch.float32)
-        if not fused:
+        training, ea, grad = self.training, self.eval_autograd, torch.is_grad_enabled()
+        # sample_and_decode's leading arguments in its order: training, eval_autograd, grad, input_rg, noise_cuda, base_fp32
+        cheap = (training, ea, grad, any([t.requires_grad for t in (noise, mu0, logvar0, g)]), noise.is_cuda,
+                 noise.dtype == torch.float32 and mu0.dtype == torch.float32 and logvar0.dtype == torch.float32)
+        out = B.sample_and_decode(*cheap) if not B.frozen_candidate(training, ea, grad) else B.ask(lambda **node: B.sample_and_decode(*cheap, **node), [
+            ("cuda_fp32", lambda: cuda_fp32(noise, mu0, logvar0, g)),
+            ("param_rg", lambda: any(t.requires_grad for t in self._all_params()))])
+        warn_eval_autograd(out.warning, 2)
+        if out.backend is Backend.FROZEN_HIP:
+            # the gradient must reach mu0 / logvar0 / noise: z by tensor ops in front of the node
+            z = noise * torch.exp(0.5 * logvar0) + mu0
+            return (z,) + tuple(self.forward(z, g, mode="direct"))
+        if out.backend is Backend.TENSOR_OPS:
             z = noise.mul(torch.exp(0.5 * logvar0)).add_(mu0)                      # models.py:77-79
             return (z,) + tuple(self.forward(z, g, mode="direct"))
         stack = self.stack()
@@ -98,22 +108,15 @@ class LocalCondRNVPDecoder(EvalAutograd, PackedWeights, nn.Module):
         (the BASELINE metric's 14-layer stack = first 14 layers of n_flows=5)."""
         if mode not in ("direct", "inverse"):
             raise ValueError(mode)
-        if use_hip_training(self, p):
-            layers = self.coupling_layers()
-            if n_layers is not None:
-                layers = layers[:int(n_layers)]
-            ps, mus, lvs = train_stack(self, layers, p, g, mode, allow_flat=n_layers is None)
-            return ps, mus, lvs
-        if self.eval_autograd == "hip":
-            layers = self.coupling_layers()
-            if n_layers is not None:
-                layers = layers[:int(n_layers)]
-            out = frozen_stack(self, self.stack, layers, p, g, mode, self.precision)
-            if out is not None:
-                return out
-        if self.training or _needs_autograd(p, g):
-            if n_layers is not None:
-                raise ValueError("n_layers is only supported on the fused eval path")
+        out, spec = choose(self, self.stack, lambda: self._layers(n_layers), self.precision, p, g, n_layers is not None)
+        warn_eval_autograd(out.warning, 2)
+        if out.backend is Backend.TRAIN_HIP:
+            return train_stack(self, self._layers(n_layers), p, g, mode, full_stack=n_layers is None)
+        if out.backend is Backend.FROZEN_HIP:
+            return run_frozen_stack(self.stack(), spec(), p, g, mode, self.precision)
+        if out.backend is Backend.ERROR:
+            raise ValueError("n_layers is only supported on the fused eval path")
+        if out.backend is Backend.TENSOR_OPS:
             return self.forward_torch(p, g, mode)
         p_out, sum_lv, ps, mus, lvs = self.stack().run(p, g, mode, self.precision,
                                                        want_lists=self.materialize_lists, n_layers=n_layers)

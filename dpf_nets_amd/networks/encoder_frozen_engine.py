@@ -43,7 +43,7 @@ def frozen_slots(enc):
 
 
 def frozen_hip_serves(enc, x):
-    """What the kernels serve (layers.wants_frozen_hip: what the call asks for): the 3 -> 64 -> [128, 256, 512] architecture, CUDA fp32 (B,3,N), bf16x3 or bf16x6."""
+    """What the kernels serve (backend.frozen_asked: what the call asks for): the 3 -> 64 -> [128, 256, 512] architecture, CUDA fp32 (B,3,N), bf16x3 or bf16x6."""
     ts = enc._layer_tensors()
     return enc.hip_supported() and enc.precision in FROZEN_PRECISIONS and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 \
         and x.shape[1] == 3 and x.shape[2] >= 1 and x.shape[0] <= 65535 \

@@ -1,35 +1,24 @@
 """PointNetCloudEncoder with the reference's constructor signature, sub-module and parameter names
 (lib/networks/encoders.py:9-28), so reference checkpoints load unchanged.
 
-forward(input (B,3,N)) -> per-point features (B,512,N):
-  * eval mode on CUDA tensors, for the architecture every config uses (3 -> 64 -> [128, 256, 512]): the fused HIP
-    kernel of csrc/encoder.hip.  The models reduce the features with `torch.max(features, dim=2)[0]`
-    (models.py:85,131,175) and use nothing else, so forward returns a `PointFeatures`: that max is answered from
-    the kernel's own (B,512) result and the (B,512,N) tensor (134 MB at B=32, N=2048) is only produced -- by the
-    same kernel with its feature output switched on -- if something else is asked of it;
-  * training mode on CUDA tensors, same architecture: forward returns a
-    `TrainPointFeatures`; its max over the points runs csrc/encoder_train.hip (batch-statistics BatchNorm, running
-    statistics updated in place, argmax kept) and is an autograd node whose backward is the HIP backward pass to
-    the twelve parameter gradients (and to the input when it requires grad).  Any other use of the features
-    materialises them with tensor ops;
-  * eval mode with `eval_autograd = "hip"`, grad mode on and the input or any encoder parameter requiring grad: forward returns a
-    `FrozenPointFeatures`; its max over the points is one autograd node -- the fused launch with the argmax switched on, and
-    csrc/encoder_frozen.hip's backward with the running statistics frozen (networks/encoder_frozen_engine.py).  Any other use
-    of the features materialises them with tensor ops, which stay differentiable.  What the kernels do not serve (CPU tensors,
-    other dtypes or widths, precision "bf16") runs tensor ops with an EvalModeAutogradWarning;
-  * eval mode with a differentiable input, other widths, BatchNorm without running statistics or with momentum=None: the
-    tensor-op path (`self.features(input)`), on PyTorch-ROCm;
-  * eval mode on CPU tensors raises (no CPU fallback).
+forward(input (B,3,N)) -> per-point features (B,512,N).  The models reduce the features with `torch.max(features, dim=2)[0]`
+(models.py:85,131,175) and use nothing else, so on the HIP backends forward returns a lazy `PointFeatures`: that max is answered
+from the kernel's own (B,512) result -- csrc/encoder.hip in eval mode, csrc/encoder_train.hip as an autograd node in training
+mode (`TrainPointFeatures`), csrc/encoder_frozen.hip with `eval_autograd = "hip"` (`FrozenPointFeatures`) -- and the (B,512,N)
+tensor (134 MB at B=32, N=2048) is only produced if something else is asked of it.  Which backend serves a call, or whether it
+is tensor ops (`forward_torch`) or refused, is networks/backend.py's encoder.
 """
 import ctypes
-import warnings
 from collections import OrderedDict
 
 import torch
 import torch.nn as nn
 
 from .._lib import lib, check, current_stream, PREC
-from .layers import SharedDot, weight_state, EvalAutograd, EvalModeAutogradWarning, wants_frozen_hip
+from . import backend as B
+from .backend import Backend
+from .encoder_frozen_engine import frozen_hip_serves, run_frozen_pool
+from .layers import SharedDot, weight_state, EvalAutograd, warn_eval_autograd
 
 _HIP_ARCH = (3, 64, (128, 256, 512))
 
@@ -245,7 +234,6 @@ class FrozenPointFeatures(PointFeatures):
             if self._full is not None:                                   # the features were asked for first
                 self._max = torch.max(self._full, dim=2)[0]
             else:
-                from .encoder_frozen_engine import run_frozen_pool
                 self._max = run_frozen_pool(self._enc, self._x)
         return self._max
 
@@ -323,26 +311,28 @@ class PointNetCloudEncoder(EvalAutograd, nn.Module):
             and len({bn.momentum for bn in bns}) == 1 and all(getattr(self.features, n).weight.dtype == torch.float32 for n in _LAYERS)
 
     def forward(self, input):
-        if self.eval_autograd == "hip":
-            from .encoder_frozen_engine import frozen_hip_serves
-            if wants_frozen_hip(self, self.parameters, input):
-                if frozen_hip_serves(self, input):
-                    return FrozenPointFeatures(self, input.contiguous())
-                warnings.warn("eval_autograd='hip': this call (CPU tensors, a dtype other than float32, another architecture or "
-                              "precision 'bf16') is served by PyTorch tensor operations, not by the HIP kernels",
-                              EvalModeAutogradWarning, stacklevel=3)
-                return self.forward_torch(input)
-        # other widths, or a differentiable input in eval mode: tensor ops
-        if not self.hip_supported() or (torch.is_grad_enabled() and input.requires_grad and not self.training):
-            return self.forward_torch(input)
-        if self.training:
-            if not self.hip_training_supported(input):
-                return self.forward_torch(input)
+        training, ea, grad = self.training, self.eval_autograd, torch.is_grad_enabled()
+        # encoder's leading arguments in its order: training, eval_autograd, grad, input_rg, cuda, layout_ok
+        cheap = (training, ea, grad, input.requires_grad, input.is_cuda,
+                 input.dtype == torch.float32 and input.dim() == 3 and input.shape[1] == 3)
+        if not B.frozen_candidate(training, ea, grad):             # the hot paths: one question, one call; both verdicts read as ever
+            arch_ok = self.hip_supported()
+            out = B.encoder(*cheap, arch_ok=arch_ok, train_serves=training and arch_ok and self.hip_training_supported(input))
+        else:
+            out = B.ask(lambda **facts: B.encoder(*cheap, **facts), [
+                ("param_rg", lambda: any(p.requires_grad for p in self.parameters())),
+                ("frozen_serves", lambda: frozen_hip_serves(self, input)), ("arch_ok", self.hip_supported)])
+        warn_eval_autograd(out.warning, 3)
+        if out.backend is Backend.FROZEN_HIP:
+            return FrozenPointFeatures(self, input.contiguous())
+        if out.backend is Backend.TRAIN_HIP:
             return TrainPointFeatures(self, input.contiguous())
-        if not input.is_cuda:
+        if out.backend is Backend.TENSOR_OPS:
+            return self.forward_torch(input)
+        if out.error == "cpu":
             raise RuntimeError("PointNetCloudEncoder: the eval-mode path runs on MI355X only (input must be a CUDA tensor); "
                                "there is no CPU fallback")
-        if input.dtype != torch.float32 or input.dim() != 3 or input.shape[1] != 3:
+        if out.error == "layout":
             raise RuntimeError("PointNetCloudEncoder: expected a float32 (B,3,N) tensor")
         return PointFeatures(self, input.contiguous())
 

@@ -2,38 +2,26 @@
 signatures, sub-module and parameter names (lib/networks/flows.py:10-160), so
 reference checkpoints load unchanged.
 
-forward(p, g, mode) -> (p_out, mu, logvar), p (B,3,N), g (B,G):
-  * eval mode (BatchNorm frozen, the per-point map of evaluate()/inference):
-    the fused HIP stack (csrc/flow.hip) -- no torch ops on the path;
-  * training mode (BatchNorm batch statistics + autograd) on CUDA tensors: the HIP
-    training kernels (csrc/flow_train.hip via networks/train_engine.py), forward and
-    backward; DPF_TRAIN_IMPL=torch selects the tensor-op restatement of
-    flows.py:95-117 instead (`forward_torch`, also what CPU tensors get: the
-    reference-shaped module the CPU tests check against the golden vectors).
+forward(p, g, mode) -> (p_out, mu, logvar), p (B,3,N), g (B,G).  Which backend serves a call -- the fused HIP stack
+(csrc/flow.hip), the HIP training kernels (networks/train_engine.py), the frozen-statistics HIP node (networks/frozen_engine.py) or
+the tensor-op restatement of flows.py:95-117 (`forward_torch`, the reference-shaped module the CPU tests check against the golden
+vectors) -- is networks/backend.py's point_flow.
 """
-import os
-
 from collections import OrderedDict
 
 import torch
 import torch.nn as nn
 
-from .layers import SharedDot, Swish, PackedWeights, EvalAutograd, EvalModeAutogradWarning, _needs_autograd, wants_frozen_hip   # noqa: F401  (re-exported)
+from . import backend as B
+from .backend import Backend, TRAIN_IMPL, TRAIN_FLAT   # noqa: F401  (re-exported; the call sites read B.TRAIN_IMPL, B.TRAIN_FLAT)
+from .layers import SharedDot, Swish, PackedWeights, EvalAutograd, EvalModeAutogradWarning, warn_eval_autograd   # noqa: F401  (re-exported)
 from .engine import FlowStack
-
-TRAIN_IMPL = os.environ.get("DPF_TRAIN_IMPL", "hip")
-
-
-def use_hip_training(module, p):
-    return module.training and p.is_cuda and TRAIN_IMPL == "hip"
-
-
-TRAIN_FLAT = os.environ.get("DPF_TRAIN_FLAT", "0") == "1"
+from .frozen_engine import cuda_fp32, run_frozen_stack, frozen_precision_ok
+from .train_engine import StackSpec, run_training_stack
 
 
 def stack_spec(owner, layers):
     """The static layout description of `layers`, cached on `owner` per number of layers."""
-    from .train_engine import StackSpec
     cache = owner.__dict__.setdefault("_train_specs", {})
     spec = cache.get(len(layers))
     if spec is None:
@@ -41,25 +29,26 @@ def stack_spec(owner, layers):
     return spec
 
 
-def frozen_stack(owner, stack, layers, p, g, mode, precision):
-    """(ps, mus, lvs) of `layers` through the frozen-statistics HIP node when the call qualifies (eval_autograd == "hip", CUDA fp32,
-    something requires grad, the f16x3 stack), else None: the caller goes on as with "torch"."""
-    from .frozen_engine import cuda_fp32, run_frozen_stack, frozen_precision_ok
-    spec = stack_spec(owner, layers)
-    if not (wants_frozen_hip(owner, spec.all_params, p, g) and cuda_fp32(p, g)):
-        return None
-    stack = stack()
-    if not frozen_precision_ok(stack, spec, precision, p.device):
-        return None
-    return run_frozen_stack(stack, spec, p, g, mode, precision)
+def choose(owner, stack, layers, precision, p, g, n_layers_given=False):
+    """(backend.point_flow's outcome for a forward(p, g) call of `owner` over `layers()`, whose fused stack is `stack()`; the
+    layers' spec where the frozen node can be asked for, built at most once per call).  B.ask reads the node's facts where they decide."""
+    training, ea, grad = owner.training, owner.eval_autograd, torch.is_grad_enabled()
+    # point_flow's leading arguments in its order: training, eval_autograd, grad, input_rg, p_cuda, train_impl, n_layers_given
+    cheap = (training, ea, grad, p.requires_grad or g.requires_grad, p.is_cuda, B.TRAIN_IMPL, n_layers_given)
+    if not B.frozen_candidate(training, ea, grad):                 # the hot paths: one question, one positional call
+        return B.point_flow(*cheap), None
+    memo = []
+    spec = lambda: memo[0] if memo else memo.append(stack_spec(owner, layers())) or memo[0]     # noqa: E731
+    return B.ask(lambda **node: B.point_flow(*cheap, **node), [
+                          ("cuda_fp32", lambda: cuda_fp32(p, g)),
+                          ("param_rg", lambda: any(t.requires_grad for t in spec().all_params())),
+                          ("precision_ok", lambda: frozen_precision_ok(stack(), spec(), precision, p.device))]), spec
 
 
-def train_stack(owner, layers, p, g, mode, allow_flat=False):
-    """Run `layers` (DIRECT order) through the HIP training path.  allow_flat: DPF_TRAIN_FLAT=1 may move the
-    parameters into a flat store on first use (the decoder passes it for its full stack only)."""
-    from .train_engine import run_training_stack
+def train_stack(owner, layers, p, g, mode, full_stack=False):
+    """Run `layers` (DIRECT order) through the HIP training path.  full_stack: the decoder's whole stack (backend.flattens)."""
     spec = stack_spec(owner, layers)
-    if allow_flat and TRAIN_FLAT and spec.flat is None:
+    if B.flattens(B.TRAIN_FLAT, full_stack) and spec.flat is None:
         spec.flatten(p.device)
     return run_training_stack(spec, p, g, mode)
 
@@ -128,17 +117,19 @@ class CondRealNVPFlow3D(EvalAutograd, PackedWeights, nn.Module):
     def forward(self, p, g, mode="direct"):
         if mode not in ("direct", "inverse"):
             raise ValueError(mode)
-        if use_hip_training(self, p):
+        stack = lambda: self.packed_stack(lambda: FlowStack([self]))           # noqa: E731
+        out, spec = choose(self, stack, lambda: [self], self.precision, p, g)
+        warn_eval_autograd(out.warning, 2)
+        if out.backend is Backend.TRAIN_HIP:
             ps, mus, lvs = train_stack(self, [self], p, g, mode)
-            return ps[0], mus[0], lvs[0]
-        if self.eval_autograd == "hip":
-            out = frozen_stack(self, lambda: self.packed_stack(lambda: FlowStack([self])), [self], p, g, mode, self.precision)
-            if out is not None:
-                return out[0][0], out[1][0], out[2][0]
-        if self.training or _needs_autograd(p, g):
+        elif out.backend is Backend.FROZEN_HIP:
+            ps, mus, lvs = run_frozen_stack(stack(), spec(), p, g, mode, self.precision)
+        elif out.backend is Backend.TENSOR_OPS:
             return self.forward_torch(p, g, mode)
-        p_out, _, ps, mus, lvs = self.packed_stack(lambda: FlowStack([self])).run(p, g, mode, self.precision, want_lists=True)
-        return p_out, mus[0], lvs[0]
+        else:
+            p_out, _, ps, mus, lvs = stack().run(p, g, mode, self.precision, want_lists=True)
+            return p_out, mus[0], lvs[0]
+        return ps[0], mus[0], lvs[0]
 
 
 class CondRealNVPFlow3DTriple(EvalAutograd, PackedWeights, nn.Module):
@@ -175,12 +166,11 @@ class CondRealNVPFlow3DTriple(EvalAutograd, PackedWeights, nn.Module):
     def forward(self, p, g, mode="direct"):
         if mode not in ("direct", "inverse"):
             raise ValueError(mode)
-        if use_hip_training(self, p):                              # the three layers as one autograd node
-            ps, mus, lvs = train_stack(self, self.layers(), p, g, mode)
-            return ps, mus, lvs
-        if self.eval_autograd == "hip":                            # the three layers as one frozen-statistics node
-            out = frozen_stack(self, lambda: self.packed_stack(lambda: FlowStack(self.layers())), self.layers(), p, g, mode,
-                               self.nvp1.precision)
-            if out is not None:
-                return out
+        stack = lambda: self.packed_stack(lambda: FlowStack(self.layers()))    # noqa: E731
+        out, spec = choose(self, stack, self.layers, self.nvp1.precision, p, g)
+        if out.backend is Backend.TRAIN_HIP:                       # the three layers as one autograd node
+            return train_stack(self, self.layers(), p, g, mode)
+        if out.backend is Backend.FROZEN_HIP:                      # the three layers as one frozen-statistics node
+            return run_frozen_stack(stack(), spec(), p, g, mode, self.nvp1.precision)
+        # FUSED, TENSOR_OPS: layer by layer, each layer asking (and warning) for itself
         return self._chain(p, g, mode, lambda lyr, pp, gg, mm: lyr(pp, gg, mode=mm))

@@ -21,7 +21,7 @@ from .flowlist import tag_layer_sum
 from .layers import scatter_param_grads
 from .train_engine import F, _T_BR, _grad_table
 
-def cuda_fp32(*tensors):                      # what the kernels of this path serve (layers.wants_frozen_hip: what the call asks for)
+def cuda_fp32(*tensors):                      # what the kernels of this path serve (backend.frozen_asked: what the call asks for)
     return all(t.is_cuda and t.dtype == torch.float32 for t in tensors)
 
 

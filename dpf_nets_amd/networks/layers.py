@@ -4,8 +4,8 @@ compatibility) and serve the training-mode path; in eval mode the coupling
 layers read the weights out of them and run the fused HIP stack instead.
 
 Also what every flow module shares around that switch: the packed-weight cache's invalidation (PackedWeights,
-weight_state), the rule that sends an eval-mode call under autograd to tensor operations (_needs_autograd), and what the three
-frozen-statistics HIP paths that replace it on request share: EvalAutograd, wants_frozen_hip, scatter_param_grads."""
+weight_state), the EvalModeAutogradWarning and its emission (networks/backend.py decides when), and what the three
+frozen-statistics HIP paths share: EvalAutograd, scatter_param_grads."""
 import warnings
 
 import torch
@@ -16,19 +16,23 @@ class EvalModeAutogradWarning(RuntimeWarning):
     """An eval()-mode module was called under autograd: the call is served by PyTorch tensor operations, not by the HIP kernels."""
 
 
-def _needs_autograd(*tensors):
-    """True when an eval()-mode call must stay differentiable with respect to its INPUTS (the reference's
-    CondRealNVPFlow3D.forward is: flows.py:95-117).  The fused HIP stacks have a backward pass for training-mode BatchNorm only
-    (csrc/flow_train.hip); an eval-mode call under autograd therefore runs the reference's op sequence on ATen (~30 kernels per
-    layer) -- correct, differentiable, and some 50x slower than the fused stack.  That is a SECOND backend behind forward(), so it
-    is loud: one EvalModeAutogradWarning per call site.  The reference's own loops never take it
-    (evaluating.py:58-59 runs under no_grad; training.py:37-56 in train() mode)."""
-    need = torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
-    if need:
-        warnings.warn("eval()-mode flow called with inputs that require grad: served by PyTorch tensor operations (differentiable, "
-                      "~30 ATen kernels per coupling layer), not by the fused HIP stack; call under torch.no_grad() for the HIP "
-                      "path, or in train() mode for the HIP training kernels", EvalModeAutogradWarning, stacklevel=3)
-    return need
+# The two messages of an EvalModeAutogradWarning (backend.Outcome.warning is the key).  "inputs": the fused stacks have a backward
+# for training-mode BatchNorm only, so an eval-mode call that must stay differentiable with respect to its INPUTS runs the reference's
+# op sequence on ATen (~30 kernels per layer) -- correct, and some 50x slower: a SECOND backend behind forward(), hence loud (VERDICT
+# r05 #7).  The reference's own loops never take it (evaluating.py:58-59 runs under no_grad; training.py:37-56 in train() mode).
+EVAL_AUTOGRAD_MESSAGES = {
+    "inputs": "eval()-mode flow called with inputs that require grad: served by PyTorch tensor operations (differentiable, "
+              "~30 ATen kernels per coupling layer), not by the fused HIP stack; call under torch.no_grad() for the HIP "
+              "path, or in train() mode for the HIP training kernels",
+    "unserved": "eval_autograd='hip': this call (CPU tensors, a dtype other than float32, another architecture or "
+                "precision 'bf16') is served by PyTorch tensor operations, not by the HIP kernels",
+}
+
+
+def warn_eval_autograd(which, stacklevel):
+    """Emit the warning an outcome names, if any.  stacklevel counts from the caller (1 = the caller's own frame)."""
+    if which is not None:
+        warnings.warn(EVAL_AUTOGRAD_MESSAGES[which], EvalModeAutogradWarning, stacklevel=stacklevel + 1)
 
 
 EVAL_AUTOGRAD = ("torch", "hip")
@@ -36,7 +40,7 @@ EVAL_AUTOGRAD = ("torch", "hip")
 
 class EvalAutograd:
     """Mixin: the `eval_autograd` attribute (extension, beside `precision`; not in the state dict).  "torch" (default): an
-    eval()-mode call whose inputs require grad is served by tensor operations, with an EvalModeAutogradWarning (_needs_autograd).
+    eval()-mode call whose inputs require grad is served by tensor operations, with an EvalModeAutogradWarning (networks/backend.py).
     "hip": an eval()-mode call on CUDA fp32 tensors where an input or ANY parameter requires grad is one autograd node over the HIP
     kernels with frozen BatchNorm statistics (networks/*frozen_engine.py), no warning.  Setting it on a decoder or a triple reaches the layers."""
     _eval_autograd = "torch"
@@ -54,13 +58,6 @@ class EvalAutograd:
             for m in (child if isinstance(child, nn.ModuleList) else [child]):
                 if isinstance(m, EvalAutograd):
                     m.eval_autograd = value
-
-
-def wants_frozen_hip(module, params, *tensors):
-    """True when an eval()-mode call of `module` asks for the frozen-statistics HIP node: eval_autograd == "hip", grad mode on, any
-    of `tensors` or of `params()` requires grad.  Whether the kernels serve it (device, dtype, shape, precision) is each path's question."""
-    return (not module.training) and module.eval_autograd == "hip" and torch.is_grad_enabled() and \
-        (any(t.requires_grad for t in tensors) or any(t.requires_grad for t in params()))
 
 
 def scatter_param_grads(block, slots, like, needs=None):

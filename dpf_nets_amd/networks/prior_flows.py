@@ -2,21 +2,10 @@
 reference's constructor signatures, sub-module, parameter and buffer names (lib/networks/flows.py:163-243,
 lib/networks/decoders.py:7-38), so reference checkpoints load unchanged.
 
-forward(g, mode):
-  * eval mode, CUDA tensors, no autograd (generation / evaluation): the whole stack in ONE HIP launch
-    (csrc/gprior.hip through dpf_gprior_forward); the lists come back as views of three (S,B,G) buffers;
-  * eval mode under autograd (latent optimisation through log p(g), fine-tuning with frozen statistics): with
-    `eval_autograd = "hip"` on the module (layers.EvalAutograd; a container hands it to the modules below it) a call on CUDA
-    fp32 tensors where g OR ANY PARAMETER requires grad is one autograd node -- that same launch forward, two launches
-    backward whatever the number of steps (csrc/gprior_frozen.hip through networks/prior_frozen_engine.py); the BatchNorm
-    buffers are only read and B = 1 is legal.  With the default "torch" a call whose g requires grad is the tensor-op
-    restatement (`forward_torch`) with an EvalModeAutogradWarning, and autograd follows the input only;
-  * training mode on CUDA tensors (GlobalRNVPDecoder): BatchNorm on the statistics of the B rows and the whole
-    backward through csrc/gprior_train.hip -- one autograd node, 4 launches per step forward and 5 backward instead
-    of ~75 tensor-op launches; DPF_TRAIN_IMPL=torch selects the tensor-op restatement (`forward_torch`), which is
-    also what CPU tensors and single RealNVPFlow / RealNVPFlowCouple modules in train() mode get.
-The kernels know RealNVPFlowCouple's two index patterns (even/odd, halves) on an even G; a RealNVPFlow with
-other warp_inds runs as tensor ops."""
+forward(g, mode): the whole stack in ONE HIP launch (csrc/gprior.hip), one training node (csrc/gprior_train.hip), one
+frozen-statistics node (csrc/gprior_frozen.hip through networks/prior_frozen_engine.py) or the tensor-op restatement
+(`forward_torch`); who serves a call is networks/backend.py's prior_flow.  The kernels know RealNVPFlowCouple's two index patterns
+(even/odd, halves) on an even G."""
 import ctypes
 from collections import OrderedDict
 
@@ -24,10 +13,13 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .layers import Swish, PackedWeights, EvalAutograd, weight_state, _needs_autograd, wants_frozen_hip, scatter_param_grads
+from . import backend as B
+from .backend import Backend
+from .layers import Swish, PackedWeights, EvalAutograd, weight_state, warn_eval_autograd, scatter_param_grads
 from .flat_store import ParamStore
 from .flowlist import FlowList, tag_layer_sum
 from .train_engine import update_running_stats
+from .prior_frozen_engine import run_frozen_prior
 from .._lib import lib, check, current_stream, MODE
 
 
@@ -89,13 +81,15 @@ class RealNVPFlow(EvalAutograd, PackedWeights, nn.Module):
     def forward(self, g, mode="direct"):
         if mode not in ("direct", "inverse"):
             raise ValueError(mode)
-        out = _frozen_prior(self, [self], g, mode)
-        if out is not None:
-            return out[0][0], out[1][0], out[2][0]
-        if _fusable(self, [self], g):
+        out = _choose(self, [self], g)
+        warn_eval_autograd(out.warning, 1)
+        if out.backend is Backend.FROZEN_HIP:
+            gs, mus, lvs = _frozen_prior(self, [self], g, mode)
+        elif out.backend is Backend.FUSED:
             _, _, gs, mus, lvs = self.packed_stack(lambda: GPriorStack([self])).run(g, mode)
-            return gs[0], mus[0], lvs[0]
-        return self.forward_torch(g, mode)
+        else:
+            return self.forward_torch(g, mode)
+        return gs[0], mus[0], lvs[0]
 
 
 class RealNVPFlowCouple(EvalAutograd, PackedWeights, nn.Module):
@@ -132,10 +126,11 @@ class RealNVPFlowCouple(EvalAutograd, PackedWeights, nn.Module):
     def forward(self, g, mode="direct"):
         if mode not in ("direct", "inverse"):
             raise ValueError(mode)
-        out = _frozen_prior(self, self.layers(), g, mode) if hasattr(self, "nvp1") else None
-        if out is not None:
-            return out
-        if _fusable(self, self.layers(), g):
+        out = _choose(self, self.layers(), g)                   # (a pattern other than 0 / 1 has no steps: AttributeError)
+        warn_eval_autograd(out.warning, 1)
+        if out.backend is Backend.FROZEN_HIP:
+            return _frozen_prior(self, self.layers(), g, mode)
+        if out.backend is Backend.FUSED:
             _, _, gs, mus, lvs = self.packed_stack(lambda: GPriorStack(self.layers())).run(g, mode)
             return list(gs.unbind(0)), list(mus.unbind(0)), list(lvs.unbind(0))
         return self.forward_torch(g, mode)
@@ -191,15 +186,14 @@ class GlobalRNVPDecoder(EvalAutograd, PackedWeights, nn.Module):
         if mode not in ("direct", "inverse"):
             raise ValueError(mode)
         steps = self.__dict__.get("_steps") or self.__dict__.setdefault("_steps", self.coupling_layers())
-        out = _frozen_prior(self, steps, g, mode)
-        if out is not None:
-            return out
-        if self.n_flows and _fusable(self, steps, g):
+        out = _choose(self, steps, g, decoder=True)
+        warn_eval_autograd(out.warning, 1)
+        if out.backend is Backend.FROZEN_HIP:
+            return _frozen_prior(self, steps, g, mode)
+        if out.backend is Backend.FUSED:
             _, sum_lv, gs, mus, lvs = self.stack().run(g, mode)
             return FlowList(gs), FlowList(mus), FlowList(lvs, sum_lv)
-        from .flows import TRAIN_IMPL
-        if self.n_flows and self.training and g.is_cuda and TRAIN_IMPL == "hip" and g.dtype == torch.float32 and \
-                self.__dict__.get("_patterns_ok", _patterns_ok(self, steps)):
+        if out.backend is Backend.TRAIN_HIP:
             return run_training_prior(self, steps, g, mode)
         return self.forward_torch(g, mode)
 
@@ -213,17 +207,16 @@ def _patterns_ok(module, layers):
     return ok
 
 
-def _fusable(module, layers, g):
-    """Eval mode on a CUDA tensor without autograd, every step one of the kernel's index patterns."""
-    if module.training:
-        return False
-    if not g.is_cuda:
-        if module.eval_autograd == "hip":                           # the HIP node was asked for and is not what serves the call
-            _needs_autograd(g)
-        return False
-    if _needs_autograd(g):                                          # as the point decoder: autograd follows the INPUT
-        return False
-    return _patterns_ok(module, layers)
+def _choose(module, layers, g, decoder=False):
+    """backend.prior_flow's outcome for a forward(g) call of `module` over `layers`; B.ask has the index patterns and the parameters
+    read only where they decide."""
+    training, ea, grad = module.training, module.eval_autograd, torch.is_grad_enabled()
+    # prior_flow's leading arguments in its order: training, eval_autograd, grad, input_rg, cuda, fp32, train_impl, has_steps, decoder
+    cheap = (training, ea, grad, g.requires_grad, g.is_cuda, g.dtype == torch.float32, B.TRAIN_IMPL, bool(layers), decoder)
+    costly = [("patterns_ok", lambda: _patterns_ok(module, layers))]
+    if B.frozen_candidate(training, ea, grad):
+        costly.append(("param_rg", lambda: any(t.requires_grad for t in _stack_plan(module, layers)[0])))
+    return B.ask(lambda **facts: B.prior_flow(*cheap, **facts), costly)
 
 
 def _stack_plan(module, layers):
@@ -240,13 +233,8 @@ def _stack_plan(module, layers):
 
 
 def _frozen_prior(module, layers, g, mode):
-    """(gs, mus, lvs) of `layers` (DIRECT order) through the frozen-statistics HIP node when the call qualifies -- eval_autograd ==
-    "hip", eval mode, a CUDA fp32 g, grad enabled, g or any parameter of the stack requires grad, the kernel's index patterns --
-    else None: the caller goes on as with "torch".  Three python lists as the training path returns them."""
-    if module.eval_autograd != "hip" or not layers or not g.is_cuda or g.dtype != torch.float32 or not _patterns_ok(module, layers) \
-            or not wants_frozen_hip(module, lambda: _stack_plan(module, layers)[0], g):
-        return None
-    from .prior_frozen_engine import run_frozen_prior
+    """(gs, mus, lvs) of `layers` (DIRECT order) through the frozen-statistics HIP node: three python lists as the training path
+    returns them."""
     params, slots, bns, total, codes, dims, eps = _stack_plan(module, layers)
     if g.dim() != 2 or g.shape[1] != dims[1]:
         raise RuntimeError("expected g (B,%d)" % dims[1])
