@@ -2247,10 +2247,10 @@ extern "C" int dpf_flow_train_backward_lists(int n_layers, int B, int N, int mod
     return dpf_graph_call(cache, (hipStream_t)stream, direct, [&](GraphKey &k) {
         k.vals(n_layers, B, N, mode, precision); k.add(meta_host, sizeof(int) * 4 * n_layers);
         k.vals(tcanon, packed, film, stats, p_in, ps, mus, logvars);
-        for (int w = 0; w < 3; ++w) {
-            const int present = tab[w] != nullptr;
+        for (const float *const *t : {g_ps, g_mus, g_lvs}) {                 // (named here: tests/test_graph_cache_cpu.py reads this fill)
+            const int present = t != nullptr;
             k.val(present);
-            if (present) k.add(tab[w], sizeof(const float *) * n_layers);      // the per-layer gradient pointers themselves
+            if (present) k.add(t, sizeof(const float *) * n_layers);           // the per-layer gradient pointers themselves
         }
         k.vals(dp_in, dp_tmp, dcanon, dfm, flow_eps, workspace);
     });
