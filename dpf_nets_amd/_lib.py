@@ -29,6 +29,10 @@ SIGNATURES = {
     "dpf_pairwise_emd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "dpf_pairwise_emd": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dpf_nndistancegrad": (_i, [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dpf_nndistancegrad_det_workspace_bytes": (_sz, [_i, _i, _i]),
+    "dpf_nndistancegrad_det": (_i, [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dpf_chamfer_cd_backward": (_i, [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dpf_chamfer_grad_lds_mode": (_i, [_i]),
     "dpf_approxmatch": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dpf_approxmatch_workspace_bytes": (_sz, [_i, _i, _i]),
     "dpf_emd_set_matrix_path": (_i, [_i]),

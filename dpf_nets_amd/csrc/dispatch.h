@@ -13,7 +13,7 @@ namespace dispatch {
 
 // ---- the switches -------------------------------------------------------------------------------------------------------
 // Every environment switch a launch path reads (the table of names, values and defaults), as the value "not set" has.
-// The three with a setter (flow_tile16, nn_small, emd_matrix_set) hold the process default of the moment in a snapshot().
+// The four with a setter (flow_tile16, nn_small, cg_lds, emd_matrix_set) hold the process default of the moment in a snapshot().
 struct Switches {
     int flow_tile16 = -1;         // DPF_FLOW_TILE16   -1: by size; 0: never the 16-point kernel; 1: whenever the precision allows
     int flow16_cw = 0;            // DPF_FLOW16_CW     0: by size; compute waves per 16-point workgroup (>= 4: 4, else 2)
@@ -25,6 +25,7 @@ struct Switches {
     int nn_ksw = 0;               // DPF_NN_KSW        0: by size; waves of a staged-scan workgroup (4 | 8, anything else 16)
     int nn_ks = 0;                // DPF_NN_KS         0: by size; 8 | 16: the sliced scan (and never the staged one)
     int nnm_qw = 0;               // DPF_NNM_QW        0: by size; waves of a matrix-core filter workgroup (4 | 8 | 16)
+    int cg_lds = -1;              // DPF_CG_LDS        -1: by size; 0: the deterministic Chamfer backward never sorts in LDS alone
     int emd_matrix_env = 1;       // DPF_EMD_MATRIX    0 only when its first character is '0': never the matrix-core family
     int emd_matrix_set = 1;       //                   dpf_emd_set_matrix_path's value (ANDed with the environment's)
     int train_split = -1;         // DPF_TRAIN_SPLIT   -1: by size; 0 / 1 forces the two-workgroups-per-branch forms
@@ -39,6 +40,7 @@ inline const Switches &env_switches() {            // filled once per process
         s.flow_tile16 = env("DPF_FLOW_TILE16", -1); s.flow16_cw = env("DPF_FLOW16_CW", 0); s.flow16_split = env("DPF_FLOW16_SPLIT", -1);
         s.flow_waves = env("DPF_FLOW_WAVES", 0); s.flow_lpb = env("DPF_FLOW_LPB", 0); s.flow_skew = env("DPF_FLOW_SKEW", 1);
         s.nn_small = env("DPF_NN_SMALL", -1); s.nn_ksw = env("DPF_NN_KSW", 0); s.nn_ks = env("DPF_NN_KS", 0); s.nnm_qw = env("DPF_NNM_QW", 0);
+        s.cg_lds = env("DPF_CG_LDS", -1);
         const char *e = getenv("DPF_EMD_MATRIX");
         s.emd_matrix_env = !(e && e[0] == '0');
         s.train_split = env("DPF_TRAIN_SPLIT", -1); s.train_roles = env("DPF_TRAIN_ROLES", -1);
@@ -48,10 +50,11 @@ inline const Switches &env_switches() {            // filled once per process
     return sw;
 }
 
-// The process defaults that have a setter (dpf_flow_set_tile16, dpf_nn_small_mode, dpf_emd_set_matrix_path), seeded from the
+// The process defaults that have a setter (dpf_flow_set_tile16, dpf_nn_small_mode, dpf_chamfer_grad_lds_mode, dpf_emd_set_matrix_path), seeded from the
 // environment, and the 16-point kernel's launch counter.  An entry reads them once, at its top: snapshot().
 struct Settable {
     std::atomic<int> flow_tile16{env_switches().flow_tile16}, nn_small{env_switches().nn_small}, emd_matrix{1};
+    std::atomic<int> cg_lds{env_switches().cg_lds};
     std::atomic<long> tile16_launches{0};
 };
 inline Settable &settable() { static Settable s; return s; }
@@ -62,6 +65,7 @@ inline Switches snapshot() {
     sw.flow_tile16 = s.flow_tile16.load(std::memory_order_relaxed);
     sw.nn_small = s.nn_small.load(std::memory_order_relaxed);
     sw.emd_matrix_set = s.emd_matrix.load(std::memory_order_relaxed);
+    sw.cg_lds = s.cg_lds.load(std::memory_order_relaxed);
     return sw;
 }
 
@@ -169,6 +173,23 @@ inline int nnm_qw(int b, int n, int m, bool force16, const Switches &sw) {
 }
 // dpf_pairwise_cd: 512-query workgroups; 256-query ones for clouds of <= 256 points (half of a 16-wave workgroup would idle)
 inline int pairwise_qw(int nmax) { return nmax <= 256 ? 8 : 16; }
+
+// ---- the deterministic Chamfer backward (chamfer_grad.hip) ------------------------------------------------------------------
+// One form per output ("targets": the points of the cloud whose gradient it is; "queries": the other cloud's, whose indices are
+// sorted).  Lds: one workgroup sorts a cloud's 32-bit keys (index << 13 | query) in LDS -- 4 bytes per key slot and 12 per
+// contribution, 128 KB of the CU's 160 at 8192 queries -- and serves all its targets alone, so their number is capped too.
+// Workspace: 64-bit keys and the contributions in the caller's scratch, any size dpf_nndistance serves.
+constexpr int CG_LDS_QUERIES = 8192;
+constexpr int CG_LDS_TARGETS = 65536;
+// a target's list of queries is added up by the thread that finds its head while it has at most this many entries (ordinary clouds:
+// one on average); a longer one (collapsed or duplicated clouds) by a wave that fetches 64 contributions at a time
+constexpr int CG_LONG_LIST = 64;
+enum class CGKernel { Lds, Workspace };
+struct CGForm { CGKernel kernel; int long_list; };
+inline CGForm cg_form(int targets, int queries, const Switches &sw) {
+    const bool lds = sw.cg_lds != 0 && queries <= CG_LDS_QUERIES && targets <= CG_LDS_TARGETS;
+    return {lds ? CGKernel::Lds : CGKernel::Workspace, CG_LONG_LIST};
+}
 
 // ---- approx-EMD (emd.hip) ---------------------------------------------------------------------------------------------------
 constexpr int EMD_MAXS = 16;     // max inner-loop slices (waves) per workgroup

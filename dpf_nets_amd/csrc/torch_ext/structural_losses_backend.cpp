@@ -92,8 +92,10 @@ std::vector<Tensor> NNDistance(Tensor set_d, Tensor set_q) {
     return {d1, i1, d2, i2};
 }
 
-// structural_loss.cpp:105-139: grad1 (B, n, 3), grad2 (B, m, 3)
-std::vector<Tensor> NNDistanceGrad(Tensor set_d, Tensor set_q, Tensor idx1, Tensor idx2, Tensor grad_dist1, Tensor grad_dist2) {
+// structural_loss.cpp:105-139: grad1 (B, n, 3), grad2 (B, m, 3); deterministic: the additions in ascending query order
+// (dpf_nndistancegrad_det, scratch allocated here like the outputs) instead of the reference's atomics
+std::vector<Tensor> NNDistanceGrad(Tensor set_d, Tensor set_q, Tensor idx1, Tensor idx2, Tensor grad_dist1, Tensor grad_dist2,
+                                   bool deterministic) {
     const Shape3 s = clouds(set_d, set_q);
     need(idx1, "idx1", at::kInt); need(idx2, "idx2", at::kInt);
     need(grad_dist1, "grad_dist1"); need(grad_dist2, "grad_dist2");
@@ -101,16 +103,49 @@ std::vector<Tensor> NNDistanceGrad(Tensor set_d, Tensor set_q, Tensor idx1, Tens
                 "expected idx1 / grad_dist1 (B, n) and idx2 / grad_dist2 (B, m)");
     c10::hip::HIPGuardMasqueradingAsCUDA guard(set_d.device());
     Tensor g1 = fresh(set_d, {s.b, s.n, 3}), g2 = fresh(set_d, {s.b, s.m, 3});
+    if (deterministic) {
+        const size_t wsb = dpf_nndistancegrad_det_workspace_bytes((int)s.b, (int)s.n, (int)s.m);
+        Tensor ws = fresh(set_d, {(int64_t)(wsb ? wsb : 8)}, at::kByte);
+        ok(dpf_nndistancegrad_det((int)s.b, (int)s.n, set_d.data_ptr<float>(), (int)s.m, set_q.data_ptr<float>(),
+                                  grad_dist1.data_ptr<float>(), idx1.data_ptr<int>(), grad_dist2.data_ptr<float>(), idx2.data_ptr<int>(),
+                                  g1.data_ptr<float>(), g2.data_ptr<float>(), ws.data_ptr(), wsb, stream_of(set_d)), "nndistancegrad_det");
+        return {g1, g2};
+    }
     ok(dpf_nndistancegrad((int)s.b, (int)s.n, set_d.data_ptr<float>(), (int)s.m, set_q.data_ptr<float>(), grad_dist1.data_ptr<float>(),
                           idx1.data_ptr<int>(), grad_dist2.data_ptr<float>(), idx2.data_ptr<int>(), g1.data_ptr<float>(),
                           g2.data_ptr<float>(), stream_of(set_d)), "nndistancegrad");
     return {g1, g2};
 }
 
+// the backward of cd (B,) = dist1.mean(1) + dist2.mean(1) in one call (dpf_chamfer_cd_backward): grad1 (B, n, 3), grad2 (B, m, 3);
+// an output that is not needed comes back undefined (None) and is not computed
+std::vector<Tensor> ChamferCDBackward(Tensor set_d, Tensor set_q, Tensor idx1, Tensor idx2, Tensor grad_cd, bool need1, bool need2) {
+    const Shape3 s = clouds(set_d, set_q);
+    need(idx1, "idx1", at::kInt); need(idx2, "idx2", at::kInt);
+    need(grad_cd, "grad_cd");
+    TORCH_CHECK(idx1.numel() == s.b * s.n && idx2.numel() == s.b * s.m && grad_cd.numel() == s.b,
+                "expected idx1 (B, n), idx2 (B, m) and grad_cd (B,)");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(set_d.device());
+    Tensor g1, g2;
+    if (need1) g1 = fresh(set_d, {s.b, s.n, 3});
+    if (need2) g2 = fresh(set_d, {s.b, s.m, 3});
+    if (!need1 && !need2) return {g1, g2};
+    const size_t wsb = dpf_nndistancegrad_det_workspace_bytes((int)s.b, (int)s.n, (int)s.m);
+    Tensor ws = fresh(set_d, {(int64_t)(wsb ? wsb : 8)}, at::kByte);
+    ok(dpf_chamfer_cd_backward((int)s.b, (int)s.n, set_d.data_ptr<float>(), (int)s.m, set_q.data_ptr<float>(), idx1.data_ptr<int>(),
+                               idx2.data_ptr<int>(), grad_cd.data_ptr<float>(), need1 ? g1.data_ptr<float>() : nullptr,
+                               need2 ? g2.data_ptr<float>() : nullptr, ws.data_ptr(), wsb, stream_of(set_d)), "chamfer_cd_backward");
+    return {g1, g2};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {        // the names of pybind/bind.cpp:9-15
+    namespace py = pybind11;
     m.def("ApproxMatch", &ApproxMatch);
     m.def("MatchCost", &MatchCost);
     m.def("MatchCostGrad", &MatchCostGrad);
     m.def("NNDistance", &NNDistance);
-    m.def("NNDistanceGrad", &NNDistanceGrad);
+    m.def("NNDistanceGrad", &NNDistanceGrad, py::arg("set_d"), py::arg("set_q"), py::arg("idx1"), py::arg("idx2"), py::arg("grad_dist1"),
+          py::arg("grad_dist2"), py::arg("deterministic") = false);
+    m.def("ChamferCDBackward", &ChamferCDBackward, py::arg("set_d"), py::arg("set_q"), py::arg("idx1"), py::arg("idx2"),
+          py::arg("grad_cd"), py::arg("need1") = true, py::arg("need2") = true);
 }

@@ -121,18 +121,61 @@ def NNDistanceCD(set_d, set_q, workspace=None):
     return [dist1, idx1, dist2, idx2, cd]
 
 
-def NNDistanceGrad(set_d, set_q, idx1, idx2, grad_dist1, grad_dist2):
-    """-> [grad1 (B,n,3), grad2 (B,m,3)]                                    structural_loss.cpp:101-124"""
+def _grad_scratch(b, n, m, dev):
+    """the deterministic backward's caller-owned scratch (nothing in it has to be zero) -> (tensor or None, pointer, bytes)"""
+    nbytes = lib().dpf_nndistancegrad_det_workspace_bytes(b, n, m)
+    if not nbytes:
+        return None, None, 0
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    return ws, ws.data_ptr(), nbytes
+
+
+def NNDistanceGrad(set_d, set_q, idx1, idx2, grad_dist1, grad_dist2, deterministic=False):
+    """-> [grad1 (B,n,3), grad2 (B,m,3)]                                    structural_loss.cpp:101-124
+    deterministic=True: the additions of the scattered term in ascending query order (dpf_nndistancegrad_det) instead of the
+    reference's atomics -- the same bits on every run, within the same tolerances."""
     _check_input(set_d, "set_d"); _check_input(set_q, "set_q")
     _check_input(idx1, "idx1", torch.int32); _check_input(idx2, "idx2", torch.int32)
     _check_input(grad_dist1, "grad_dist1"); _check_input(grad_dist2, "grad_dist2")
     b, n, m = _dims(set_d, set_q)
+    if deterministic and (idx1.numel() != b * n or grad_dist1.numel() != b * n or idx2.numel() != b * m or grad_dist2.numel() != b * m):
+        raise RuntimeError("expected idx1 / grad_dist1 (B, n) and idx2 / grad_dist2 (B, m)")
     grad1 = torch.empty((b, n, 3), dtype=torch.float32, device=set_d.device)
     grad2 = torch.empty((b, m, 3), dtype=torch.float32, device=set_d.device)
     with torch.cuda.device(set_d.device):
-        check(lib().dpf_nndistancegrad(b, n, set_d.data_ptr(), m, set_q.data_ptr(), grad_dist1.data_ptr(),
-                                       idx1.data_ptr(), grad_dist2.data_ptr(), idx2.data_ptr(), grad1.data_ptr(),
-                                       grad2.data_ptr(), current_stream()), "nndistancegrad")
+        if deterministic:
+            ws, wsp, nbytes = _grad_scratch(b, n, m, set_d.device)
+            check(lib().dpf_nndistancegrad_det(b, n, set_d.data_ptr(), m, set_q.data_ptr(), grad_dist1.data_ptr(),
+                                               idx1.data_ptr(), grad_dist2.data_ptr(), idx2.data_ptr(), grad1.data_ptr(),
+                                               grad2.data_ptr(), wsp, nbytes, current_stream()), "nndistancegrad_det")
+        else:
+            check(lib().dpf_nndistancegrad(b, n, set_d.data_ptr(), m, set_q.data_ptr(), grad_dist1.data_ptr(),
+                                           idx1.data_ptr(), grad_dist2.data_ptr(), idx2.data_ptr(), grad1.data_ptr(),
+                                           grad2.data_ptr(), current_stream()), "nndistancegrad")
+    return [grad1, grad2]
+
+
+def ChamferCDBackward(set_d, set_q, idx1, idx2, grad_cd, need1=True, need2=True):
+    """The backward of cd (B,) = dist1.mean(1) + dist2.mean(1) in one call -> [grad1 (B,n,3) | None, grad2 (B,m,3) | None]:
+    NNDistanceGrad(deterministic=True) with grad_dist1 = grad_cd / n and grad_dist2 = grad_cd / m, neither of them materialised
+    (dpf_chamfer_cd_backward).  An output that is not needed is neither computed nor allocated."""
+    _check_input(set_d, "set_d"); _check_input(set_q, "set_q")
+    _check_input(idx1, "idx1", torch.int32); _check_input(idx2, "idx2", torch.int32)
+    _check_input(grad_cd, "grad_cd")
+    b, n, m = _dims(set_d, set_q)
+    if idx1.numel() != b * n or idx2.numel() != b * m or grad_cd.numel() != b:
+        raise RuntimeError("expected idx1 (B, n), idx2 (B, m) and grad_cd (B,)")
+    dev = set_d.device
+    grad1 = torch.empty((b, n, 3), dtype=torch.float32, device=dev) if need1 else None
+    grad2 = torch.empty((b, m, 3), dtype=torch.float32, device=dev) if need2 else None
+    if not (need1 or need2):
+        return [None, None]
+    with torch.cuda.device(dev):
+        ws, wsp, nbytes = _grad_scratch(b, n, m, dev)
+        check(lib().dpf_chamfer_cd_backward(b, n, set_d.data_ptr(), m, set_q.data_ptr(), idx1.data_ptr(), idx2.data_ptr(),
+                                            grad_cd.data_ptr(), grad1.data_ptr() if need1 else None,
+                                            grad2.data_ptr() if need2 else None, wsp, nbytes, current_stream()),
+              "chamfer_cd_backward")
     return [grad1, grad2]
 
 

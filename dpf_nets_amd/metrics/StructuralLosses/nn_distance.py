@@ -5,6 +5,15 @@ import torch
 from .StructuralLossesBackend import NNDistance, NNDistanceGrad
 
 
+# None: the backward follows torch.are_deterministic_algorithms_enabled(); True / False: the deterministic entry
+# (NNDistanceGrad(deterministic=True): additions in ascending query order) always / never
+DETERMINISTIC_BACKWARD = None
+
+
+def deterministic_backward():
+    return torch.are_deterministic_algorithms_enabled() if DETERMINISTIC_BACKWARD is None else bool(DETERMINISTIC_BACKWARD)
+
+
 class NNDistanceFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, seta, setb):
@@ -18,7 +27,8 @@ class NNDistanceFunction(torch.autograd.Function):
     def backward(ctx, grad_dist1, grad_dist2):
         seta, setb = ctx.saved_tensors
         grada, gradb = NNDistanceGrad(seta, setb, ctx.idx1, ctx.idx2,
-                                      grad_dist1.contiguous(), grad_dist2.contiguous())
+                                      grad_dist1.contiguous(), grad_dist2.contiguous(),
+                                      deterministic=deterministic_backward())
         return grada, gradb
 
 

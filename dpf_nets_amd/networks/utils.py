@@ -80,6 +80,40 @@ def chamfer_cd_per_cloud(pred, true):
     return _default_evaluator.cd(pred, true)
 
 
+class ChamferLossFunction(torch.autograd.Function):
+    """cd (B,) as ONE autograd node: forward = the evaluator's single launch (the bits of chamfer_cd_per_cloud), backward = one
+    dpf_chamfer_cd_backward call for the inputs that need a gradient, its additions in a fixed order (the same bits every run)."""
+
+    @staticmethod
+    def forward(ctx, pred, true, evaluator):
+        dist1, idx1, dist2, idx2, cd = evaluator(pred, true)
+        ctx.save_for_backward(pred, true)
+        ctx.idx1, ctx.idx2 = idx1, idx2          # indices ride on ctx, as in NNDistanceFunction
+        return cd
+
+    @staticmethod
+    def backward(ctx, grad_cd):
+        from ..metrics.StructuralLosses.StructuralLossesBackend import ChamferCDBackward
+        pred, true = ctx.saved_tensors
+        g1, g2 = ChamferCDBackward(pred, true, ctx.idx1, ctx.idx2, grad_cd.contiguous(),
+                                   need1=ctx.needs_input_grad[0], need2=ctx.needs_input_grad[1])
+        return g1, g2, None
+
+
+def chamfer_loss(pred, true, evaluator=None):
+    """(B,) Chamfer distance of each pair of clouds, cd[b] = dist1[b].mean() + dist2[b].mean(), WITH autograd: the value of
+    chamfer_cd_per_cloud (one launch) and a deterministic one-call backward that computes only the gradients that are asked for.
+    (B, n, 3), (B, m, 3) contiguous float32 CUDA tensors, anything else raises; evaluator: a ChamferEvaluator (default: the process-wide one)."""
+    global _default_evaluator
+    from ..metrics.StructuralLosses.StructuralLossesBackend import _check_input
+    _check_input(pred, "pred"); _check_input(true, "true")          # (as NNDistanceCD: RuntimeError for a CPU tensor or another dtype)
+    if evaluator is None:
+        if _default_evaluator is None:
+            _default_evaluator = ChamferEvaluator()
+        evaluator = _default_evaluator
+    return ChamferLossFunction.apply(pred, true, evaluator)
+
+
 def f_score(predicted_clouds, true_clouds, threshold=0.001):
     """lib/networks/utils.py:38-42.  Without autograd the thresholds, means and the F1 formula are one launch over the two
     distance rows (dpf_fscore_reduce: integer counts, the float arithmetic in the reference's order)."""

@@ -94,6 +94,35 @@ int dpf_nndistancegrad(int b, int n, const float *xyz1, int m, const float *xyz2
                        const float *grad_dist2, const int *idx2,
                        float *grad_xyz1, float *grad_xyz2, dpf_stream_t stream);
 
+/* dpf_nndistancegrad with a DEFINED order of additions: the same bits on every run (csrc/chamfer_grad.hip; no float atomics).
+ * Per cloud, every operation a separately rounded fp32 one (no FMA contraction):
+ *   grad_xyz1[j] = (2*grad_dist1[j]) * (xyz1[j] - xyz2[idx1[j]])                                     (the direct term), then
+ *   grad_xyz1[idx2[l]] = grad_xyz1[idx2[l]] + (-((2*grad_dist2[l]) * (xyz2[l] - xyz1[idx2[l]])))     for l = 0 .. m-1 ASCENDING;
+ * grad_xyz2 the same with the clouds swapped (direct term from grad_dist2 / idx2, then j = 0 .. n-1 ascending).  This is one of
+ * the orders dpf_nndistancegrad may produce, so its tolerances hold.  grad_xyz1 or grad_xyz2 may be NULL: that gradient is
+ * neither computed nor written.  Serves every size dpf_nndistance serves (3n, 3m < 2^31, b <= 65535; n != m included); an index
+ * outside its cloud is read as the nearest valid one.
+ * workspace: dpf_nndistancegrad_det_workspace_bytes(b, n, m) bytes, 8-byte aligned, caller-owned; 0 bytes (NULL allowed) while the
+ * clouds are sorted in LDS (<= 8192 queries and <= 65536 targets per output).  It may come in dirty and is left dirty: nothing
+ * in it has to be zero, the call writes every word it reads.  No allocation, no host synchronisation: capture-safe. */
+size_t dpf_nndistancegrad_det_workspace_bytes(int b, int n, int m);
+int dpf_nndistancegrad_det(int b, int n, const float *xyz1, int m, const float *xyz2,
+                           const float *grad_dist1, const int *idx1,
+                           const float *grad_dist2, const int *idx2,
+                           float *grad_xyz1, float *grad_xyz2,
+                           void *workspace, size_t workspace_bytes, dpf_stream_t stream);
+/* The same for the per-cloud Chamfer distance cd[i] = mean(dist1[i]) + mean(dist2[i]): grad_dist1[i][j] = grad_cd[i] / (float)n and
+ * grad_dist2[i][l] = grad_cd[i] / (float)m (correctly rounded fp32 divisions, what autograd's mean hands back); no (B, n) row is
+ * read.  Same workspace, same NULL rule: one output is the common case (the target cloud does not require a gradient). */
+int dpf_chamfer_cd_backward(int b, int n, const float *xyz1, int m, const float *xyz2,
+                            const int *idx1, const int *idx2, const float *grad_cd,
+                            float *grad_xyz1, float *grad_xyz2,
+                            void *workspace, size_t workspace_bytes, dpf_stream_t stream);
+/* Which form serves them: -1 = by size (default; env DPF_CG_LDS), 0 = never the LDS-only form (every output sorts in the
+ * workspace), 1 = as -1.  Same bits.  Returns the previous mode; an atomic process default for tests and tools, like
+ * dpf_nn_small_mode (ask dpf_nndistancegrad_det_workspace_bytes after setting it). */
+int dpf_chamfer_grad_lds_mode(int mode);
+
 /* replaces approxmatch(...)     src/approxmatch.cuh:6, approxmatch.cu:299-307.
  * match: (b, m, n) fp32, fully overwritten.  temp: (b, 2*(n+m)) fp32 scratch
  * (remainL | remainR | ratioL | ratioR per cloud, approxmatch.cu:4). */
