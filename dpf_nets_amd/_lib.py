@@ -119,6 +119,10 @@ SIGNATURES = {
     "dpf_mesh_cdf_build": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _sz, _vp]),
     "dpf_mesh_variates": (_i, [_i, _i, ctypes.c_ulonglong, ctypes.c_ulonglong, _vp, _vp, _vp, _vp]),
     "dpf_mesh_sample": (_i, [_i] + [_vp] * 8 + [_i, _i] + [_vp] * 4 + [_i, _i, _f, _f, _f, _f] + [_vp] * 4),
+    "dpf_point_mesh_tile": (_i, []),
+    "dpf_point_mesh_workspace_bytes": (_sz, [_i, _i]),
+    "dpf_point_mesh_distance": (_i, [_i] + [_vp] * 5 + [_i, _i, _vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dpf_point_mesh_distance_grad": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dpf_version": (ctypes.c_char_p, []),
 }
 

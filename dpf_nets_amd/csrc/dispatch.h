@@ -268,5 +268,26 @@ inline TrainForm train_form(int ns, int nblk, int n_cu, const Switches &sw) {
     return f;
 }
 
+// ---- point-to-mesh distance (point_mesh.hip) --------------------------------------------------------------------------------
+constexpr int PM_WG_POINTS = 256;   // query points of a workgroup: 4 waves, one point per lane
+constexpr int PM_TILE = 256;        // faces per LDS tile (16 KB of staged faces)
+constexpr int PM_FILL_WGS = 512;    // workgroups that fill the chip: two per CU (profiles/point_mesh_forms.txt)
+constexpr int PM_MAX_SPLITS = 1024;
+// Whole: every workgroup walks all tiles of its slot's mesh.  Split: the tiles are dealt round-robin to `splits` workgroups per
+// 256 points (64-bit atomic minimum, then a finishing launch) -- where the points alone leave CUs idle, as many splits as bring
+// the launch to PM_FILL_WGS workgroups, never more than the largest mesh has tiles.  force: 0 by size, 1 Whole, 2 Split (with
+// the splits the sizes ask for, at least one).  Total: any arguments give a form with 1 <= splits <= PM_MAX_SPLITS.
+enum class PMKernel { Whole, Split };
+struct PMForm { PMKernel kernel; int splits; };
+inline PMForm pm_form(int b, int n, long max_faces, int force) {
+    const long wgs = (b > 0 ? (long)b : 1) * (n > 0 ? ceil_div(n, PM_WG_POINTS) : 1);
+    const long tiles = max_faces > 0 ? ceil_div(max_faces, PM_TILE) : 1;
+    long splits = wgs >= PM_FILL_WGS ? 1 : ceil_div(PM_FILL_WGS, wgs);
+    if (splits > tiles) splits = tiles;
+    if (splits > PM_MAX_SPLITS) splits = PM_MAX_SPLITS;
+    if (force == 1 || (force != 2 && splits < 2)) return {PMKernel::Whole, 1};
+    return {PMKernel::Split, (int)splits};
+}
+
 }  // namespace dispatch
 #endif  // DPF_DISPATCH_H

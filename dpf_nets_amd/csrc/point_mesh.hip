@@ -1,0 +1,316 @@
+// Exact squared distance from query points to the triangle meshes of the device mesh store (datasets.MeshStore): for every
+// point the minimum over the faces of its slot's mesh of the squared distance to the closed triangle, a face that attains it
+// and the closest point on that face.  Brute force, B * N * F point-triangle tests, the faces broadcast from LDS.
+//
+// The contract is in include/dpf_hip.h; in short
+//   pm_stage -- per face, once per tile and workgroup: 16 floats every lane of a wave shares (corner a, the edge vectors
+//               ab = b - a and ac = c - a, their dot products aa, g = ab.ac, cc, and the reciprocals 1/aa, 1/cc, 1/|c - b|^2,
+//               1/det with det = aa * cc - g * g).  A face is THIN when !(det > 2^-14 * (aa * cc)): degenerate faces (zero area,
+//               repeated vertices) and slivers whose determinant is mostly rounding; its 1/det is stored as 0.
+//   pm_eval  -- per (point, face): Ericson's region classification (Real-Time Collision Detection, 5.1.5) on d1 = ab.ap,
+//               d2 = ac.ap and the staged dot products -- d3 = d1 - aa, d4 = d2 - g, d5 = d1 - g, d6 = d2 - cc, vb = cc * d1 - g * d2,
+//               vc = aa * d2 - g * d1 -- as a chain of selects; every quotient is a product with a staged reciprocal, so a pair
+//               costs no division.  A thin face is the nearest of its three edges (segments, or points where an edge has no
+//               length), ties to AB, then AC, then BC.  The closest point is q = a + v * ab + w * ac, the distance |p - q|^2.
+//   the minimum -- (distance bits << 32 | face) as an unsigned 64-bit key: non-negative fp32 bit patterns order as the floats
+//               do, the lowest face index wins among equal distances, and a minimum does not depend on the order it is taken in.
+//
+// Two kernel forms (dispatch.h: pm_form).  Whole: a workgroup of 4 waves holds 256 points of one slot, one per lane, and walks
+// every tile of the slot's mesh.  Split: the tiles of a mesh are dealt round-robin to `splits` workgroups per 256 points, each
+// folds its minimum into a key buffer pre-set to all-ones with a 64-bit vector atomic minimum, and a finishing launch unpacks
+// the key and recomputes the closest point on the winning face with the same pm_stage / pm_eval.
+//
+// Compiled with -ffp-contract=off: the fused operations are the fmaf calls written out below and no others, so both forms and
+// the finishing pass round alike.  fp32 division (staging only) is the correctly rounded one.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "dpf_hip.h"
+#include "dispatch.h"
+
+namespace {
+
+constexpr int PM_THREADS = dispatch::PM_WG_POINTS;  // threads = points of a workgroup: one point per lane, 4 waves
+constexpr int PM_TILE = dispatch::PM_TILE;          // faces per LDS tile: one face staged per thread
+constexpr int PM_MAX_SLOTS = 32768;                 // batch slots per launch (grid.y)
+constexpr long PM_MAX_BLOCKS = 1L << 22;            // point chunks per launch (grid.x)
+constexpr float PM_THIN = 6.103515625e-05f;         // 2^-14
+
+static_assert(PM_TILE == PM_THREADS, "one thread stages one face of a tile");
+
+struct PMStore {
+    int M;
+    const float *vertices;
+    const long *vertex_bounds;
+    const unsigned int *faces;
+    const long *face_bounds;
+    const unsigned int *flags;
+};
+
+// what the lanes of a wave share about a face
+struct PMFace {
+    float ax, ay, az, aa;
+    float abx, aby, abz, g;
+    float acx, acy, acz, cc;
+    float iaa, icc, ibc, idet;
+};
+
+__device__ __forceinline__ float pm_dot(float ax, float ay, float az, float bx, float by, float bz) {
+    return fmaf(az, bz, fmaf(ay, by, ax * bx));
+}
+
+__device__ __forceinline__ PMFace pm_stage(const float *v0, const float *v1, const float *v2) {
+    PMFace f;
+    f.ax = v0[0]; f.ay = v0[1]; f.az = v0[2];
+    f.abx = v1[0] - f.ax; f.aby = v1[1] - f.ay; f.abz = v1[2] - f.az;
+    f.acx = v2[0] - f.ax; f.acy = v2[1] - f.ay; f.acz = v2[2] - f.az;
+    f.aa = pm_dot(f.abx, f.aby, f.abz, f.abx, f.aby, f.abz);
+    f.g = pm_dot(f.abx, f.aby, f.abz, f.acx, f.acy, f.acz);
+    f.cc = pm_dot(f.acx, f.acy, f.acz, f.acx, f.acy, f.acz);
+    const float ex = f.acx - f.abx, ey = f.acy - f.aby, ez = f.acz - f.abz;
+    const float bb = pm_dot(ex, ey, ez, ex, ey, ez);
+    const float det = fmaf(f.aa, f.cc, -(f.g * f.g));
+    f.iaa = f.aa > 0.0f ? 1.0f / f.aa : 0.0f;
+    f.icc = f.cc > 0.0f ? 1.0f / f.cc : 0.0f;
+    f.ibc = bb > 0.0f ? 1.0f / bb : 0.0f;
+    f.idet = det > PM_THIN * (f.aa * f.cc) ? 1.0f / det : 0.0f;
+    return f;
+}
+
+__device__ __forceinline__ float pm_clamp01(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }     // (a NaN becomes 0)
+
+// q = a + v * ab + w * ac and |p - q|^2
+__device__ __forceinline__ float pm_point(const PMFace &f, float px, float py, float pz, float v, float w, float &qx, float &qy,
+                                          float &qz) {
+    qx = fmaf(w, f.acx, fmaf(v, f.abx, f.ax));
+    qy = fmaf(w, f.acy, fmaf(v, f.aby, f.ay));
+    qz = fmaf(w, f.acz, fmaf(v, f.abz, f.az));
+    const float dx = px - qx, dy = py - qy, dz = pz - qz;
+    return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+}
+
+__device__ __forceinline__ float pm_eval(const PMFace &f, float px, float py, float pz, float &qx, float &qy, float &qz) {
+    const float apx = px - f.ax, apy = py - f.ay, apz = pz - f.az;
+    const float d1 = pm_dot(f.abx, f.aby, f.abz, apx, apy, apz), d2 = pm_dot(f.acx, f.acy, f.acz, apx, apy, apz);
+    const float d3 = d1 - f.aa, d4 = d2 - f.g, d5 = d1 - f.g, d6 = d2 - f.cc;
+    const float tab = pm_clamp01(d1 * f.iaa), tac = pm_clamp01(d2 * f.icc), tbc = pm_clamp01((d4 - d3) * f.ibc);
+    if (f.idet == 0.0f) {                                                   // a thin face: the nearest of its three edges (the same for every lane)
+        float d = pm_point(f, px, py, pz, tab, 0.0f, qx, qy, qz);
+        float x, y, z;
+        float e = pm_point(f, px, py, pz, 0.0f, tac, x, y, z);
+        if (e < d) { d = e; qx = x; qy = y; qz = z; }
+        e = pm_point(f, px, py, pz, 1.0f - tbc, tbc, x, y, z);
+        if (e < d) { d = e; qx = x; qy = y; qz = z; }
+        return d;
+    }
+    const float vb = fmaf(f.cc, d1, -(f.g * d2)), vc = fmaf(f.aa, d2, -(f.g * d1));
+    float v = vb * f.idet, w = vc * f.idet;                                // inside the triangle
+    bool c = v + w >= 1.0f && d4 - d3 >= 0.0f && d5 - d6 >= 0.0f;           // edge BC (va <= 0)
+    v = c ? 1.0f - tbc : v; w = c ? tbc : w;
+    c = vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f;                             // edge AC
+    v = c ? 0.0f : v; w = c ? tac : w;
+    c = d6 >= 0.0f && d5 <= d6;                                             // corner C
+    v = c ? 0.0f : v; w = c ? 1.0f : w;
+    c = vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f;                             // edge AB
+    v = c ? tab : v; w = c ? 0.0f : w;
+    c = d3 >= 0.0f && d4 <= d3;                                             // corner B
+    v = c ? 1.0f : v; w = c ? 0.0f : w;
+    c = d1 <= 0.0f && d2 <= 0.0f;                                           // corner A
+    v = c ? 0.0f : v; w = c ? 0.0f : w;
+    v = pm_clamp01(v);                                                      // whatever rounding did to the classification,
+    w = fminf(fmaxf(w, 0.0f), 1.0f - v);                                    // q lies on the closed triangle
+    return pm_point(f, px, py, pz, v, w, qx, qy, qz);
+}
+
+struct PMSlot { bool ok; long fb, vb; int F; };
+
+__device__ __forceinline__ PMSlot pm_slot(const PMStore &st, const int *mesh_idx, size_t b) {
+    PMSlot s{false, 0, 0, 0};
+    const int m = mesh_idx[b];
+    if (m < 0 || m >= st.M || st.flags[m] != 0u) return s;                  // nothing of such a mesh is read
+    s.fb = st.face_bounds[m]; s.vb = st.vertex_bounds[m];
+    s.F = (int)(st.face_bounds[m + 1] - s.fb);
+    s.ok = s.F >= 1;
+    return s;
+}
+
+__device__ __forceinline__ PMFace pm_stage_face(const PMStore &st, const PMSlot &s, int face) {
+    const unsigned int *fi = st.faces + (size_t)(s.fb + face) * 3;          // validated by dpf_mesh_cdf_build: flags[m] == 0
+    return pm_stage(st.vertices + (size_t)(s.vb + fi[0]) * 3, st.vertices + (size_t)(s.vb + fi[1]) * 3,
+                    st.vertices + (size_t)(s.vb + fi[2]) * 3);
+}
+
+__device__ __forceinline__ bool pm_finite(float x, float y, float z) {
+    return fabsf(x) <= 3.402823466e38f && fabsf(y) <= 3.402823466e38f && fabsf(z) <= 3.402823466e38f;   // (false for NaN)
+}
+
+// the outputs of one point from its key
+__device__ __forceinline__ void pm_write(const PMStore &st, const PMSlot &s, bool finite, unsigned long long key, float px, float py,
+                                         float pz, size_t at, float *dist, int *face, float *closest) {
+    const float nan = __builtin_nanf("");
+    float d = nan, qx = nan, qy = nan, qz = nan;
+    int k = -1;
+    if (s.ok && finite) {
+        k = (int)(unsigned int)key;
+        const PMFace f = pm_stage_face(st, s, k);
+        pm_eval(f, px, py, pz, qx, qy, qz);
+        d = __uint_as_float((unsigned int)(key >> 32));
+    }
+    dist[at] = d;
+    face[at] = k;
+    if (closest) { closest[at * 3] = qx; closest[at * 3 + 1] = qy; closest[at * 3 + 2] = qz; }
+}
+
+// tiles t0, t0 + stride, ... of the slot's mesh; SPLIT: the minimum goes into keys, else straight to the outputs
+template <bool SPLIT>
+__global__ __launch_bounds__(PM_THREADS) void pm_kernel(PMStore st, int N, const float *__restrict__ points, const int *mesh_idx,
+                                                        int b0, long blk0, unsigned long long *keys, float *dist, int *face,
+                                                        float *closest) {
+    __shared__ float4 q0[PM_TILE], q1[PM_TILE], q2[PM_TILE], q3[PM_TILE];   // structure of arrays: a lane-uniform index broadcasts
+    const int tid = threadIdx.x;
+    const size_t b = (size_t)b0 + blockIdx.y;
+    const long n = (blk0 + blockIdx.x) * PM_THREADS + tid;
+    const size_t at = b * (size_t)N + (size_t)n;
+    const PMSlot s = pm_slot(st, mesh_idx, b);
+    float px = 0.0f, py = 0.0f, pz = 0.0f;
+    bool finite = false;
+    if (n < N) {
+        px = points[at * 3]; py = points[at * 3 + 1]; pz = points[at * 3 + 2];
+        finite = pm_finite(px, py, pz);
+        if (!finite) px = py = pz = 0.0f;
+    }
+    unsigned int best = 0xffffffffu, bestf = 0xffffffffu;
+    if (s.ok) {                                                             // (the same for the whole workgroup)
+        const int ntiles = (s.F + PM_TILE - 1) / PM_TILE;
+        const int t0 = SPLIT ? (int)blockIdx.z : 0, stride = SPLIT ? (int)gridDim.z : 1;
+        for (int t = t0; t < ntiles; t += stride) {
+            const int base = t * PM_TILE, cnt = s.F - base < PM_TILE ? s.F - base : PM_TILE;
+            __syncthreads();
+            if (tid < cnt) {
+                const PMFace f = pm_stage_face(st, s, base + tid);
+                q0[tid] = make_float4(f.ax, f.ay, f.az, f.aa);
+                q1[tid] = make_float4(f.abx, f.aby, f.abz, f.g);
+                q2[tid] = make_float4(f.acx, f.acy, f.acz, f.cc);
+                q3[tid] = make_float4(f.iaa, f.icc, f.ibc, f.idet);
+            }
+            __syncthreads();
+#pragma unroll 2
+            for (int j = 0; j < cnt; ++j) {
+                const float4 a0 = q0[j], a1 = q1[j], a2 = q2[j], a3 = q3[j];
+                const PMFace f{a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, a2.x, a2.y, a2.z, a2.w, a3.x, a3.y, a3.z, a3.w};
+                float qx, qy, qz;
+                const unsigned int d = __float_as_uint(pm_eval(f, px, py, pz, qx, qy, qz));
+                const bool lower = d < best;                                // faces come in ascending order: strict keeps the lowest index
+                best = lower ? d : best;
+                bestf = lower ? (unsigned int)(base + j) : bestf;
+            }
+        }
+    }
+    if (n >= N) return;
+    const unsigned long long key = ((unsigned long long)best << 32) | bestf;
+    if (SPLIT) {
+        if (s.ok && finite && bestf != 0xffffffffu) atomicMin(&keys[at], key);
+    } else {
+        pm_write(st, s, finite, key, px, py, pz, at, dist, face, closest);
+    }
+}
+
+__global__ __launch_bounds__(PM_THREADS) void pm_fill_kernel(unsigned long long *keys, size_t i0, size_t n) {
+    const size_t i = i0 + (size_t)blockIdx.x * PM_THREADS + threadIdx.x;
+    if (i < n) keys[i] = ~0ull;
+}
+
+__global__ __launch_bounds__(PM_THREADS) void pm_finish_kernel(PMStore st, int N, const float *__restrict__ points, const int *mesh_idx,
+                                                               int b0, long blk0, const unsigned long long *keys, float *dist, int *face,
+                                                               float *closest) {
+    const size_t b = (size_t)b0 + blockIdx.y;
+    const long n = (blk0 + blockIdx.x) * PM_THREADS + threadIdx.x;
+    if (n >= N) return;
+    const size_t at = b * (size_t)N + (size_t)n;
+    const PMSlot s = pm_slot(st, mesh_idx, b);
+    const float px = points[at * 3], py = points[at * 3 + 1], pz = points[at * 3 + 2];
+    pm_write(st, s, pm_finite(px, py, pz), keys[at], px, py, pz, at, dist, face, closest);
+}
+
+__global__ __launch_bounds__(PM_THREADS) void pm_grad_kernel(size_t i0, size_t n, const float *__restrict__ points,
+                                                             const float *__restrict__ closest, const float *__restrict__ grad_dist,
+                                                             float *__restrict__ grad_points) {
+    const size_t i = i0 + (size_t)blockIdx.x * PM_THREADS + threadIdx.x;    // one thread per point
+    if (i >= n) return;
+    const float g2 = 2.0f * grad_dist[i];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float q = closest[i * 3 + c];
+        grad_points[i * 3 + c] = q == q ? g2 * (points[i * 3 + c] - q) : 0.0f;          // no closest point (NaN): no gradient
+    }
+}
+
+}  // namespace
+
+extern "C" int dpf_point_mesh_tile(void) { return PM_TILE; }
+
+extern "C" size_t dpf_point_mesh_workspace_bytes(int B, int N) {
+    if (B < 1 || N < 1) return 0;
+    return (size_t)B * (size_t)N * sizeof(unsigned long long);
+}
+
+extern "C" int dpf_point_mesh_distance(int M, const float *vertices, const long *vertex_bounds, const unsigned int *faces,
+                                       const long *face_bounds, const unsigned int *flags, int B, int N, const float *points,
+                                       const int *mesh_idx, long max_faces, int form, float *dist, int *face, float *closest,
+                                       void *workspace, size_t workspace_bytes, dpf_stream_t stream) {
+    if (B < 0 || N < 0 || form < 0 || form > 2) return DPF_EINVAL;
+    if (B == 0 || N == 0) return 0;
+    if (M < 1 || !vertices || !vertex_bounds || !faces || !face_bounds || !flags || !points || !mesh_idx || !dist || !face)
+        return DPF_EINVAL;
+    if (max_faces < 1) return DPF_EINVAL;
+    const dispatch::PMForm pf = dispatch::pm_form(B, N, max_faces, form);
+    const bool split = pf.kernel == dispatch::PMKernel::Split;
+    unsigned long long *keys = (unsigned long long *)workspace;
+    if (split && (!keys || ((uintptr_t)keys & 7) || workspace_bytes < dpf_point_mesh_workspace_bytes(B, N))) return DPF_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e;
+    const PMStore st{M, vertices, vertex_bounds, faces, face_bounds, flags};
+    if (split) {
+        const size_t n = (size_t)B * (size_t)N, per = (size_t)PM_MAX_BLOCKS * PM_THREADS;
+        for (size_t i0 = 0; i0 < n; i0 += per) {
+            const size_t cnt = n - i0 < per ? n - i0 : per;
+            hipLaunchKernelGGL(pm_fill_kernel, dim3((unsigned)((cnt + PM_THREADS - 1) / PM_THREADS)), dim3(PM_THREADS), 0, s, keys, i0, n);
+            if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+        }
+    }
+    const long nblk = dispatch::ceil_div(N, PM_THREADS);
+    for (int pass = 0; pass < (split ? 2 : 1); ++pass)
+        for (int b0 = 0; b0 < B; b0 += PM_MAX_SLOTS) {
+            const unsigned nb = (unsigned)(B - b0 < PM_MAX_SLOTS ? B - b0 : PM_MAX_SLOTS);
+            for (long k0 = 0; k0 < nblk; k0 += PM_MAX_BLOCKS) {
+                const unsigned nk = (unsigned)(nblk - k0 < PM_MAX_BLOCKS ? nblk - k0 : PM_MAX_BLOCKS);
+                if (!split)
+                    hipLaunchKernelGGL(pm_kernel<false>, dim3(nk, nb), dim3(PM_THREADS), 0, s, st, N, points, mesh_idx, b0, k0, keys, dist,
+                                       face, closest);
+                else if (pass == 0)
+                    hipLaunchKernelGGL(pm_kernel<true>, dim3(nk, nb, (unsigned)pf.splits), dim3(PM_THREADS), 0, s, st, N, points, mesh_idx,
+                                       b0, k0, keys, dist, face, closest);
+                else
+                    hipLaunchKernelGGL(pm_finish_kernel, dim3(nk, nb), dim3(PM_THREADS), 0, s, st, N, points, mesh_idx, b0, k0, keys, dist,
+                                       face, closest);
+                if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+            }
+        }
+    return 0;
+}
+
+extern "C" int dpf_point_mesh_distance_grad(int B, int N, const float *points, const float *closest, const float *grad_dist,
+                                            float *grad_points, dpf_stream_t stream) {
+    if (B < 0 || N < 0) return DPF_EINVAL;
+    if (B == 0 || N == 0) return 0;
+    if (!points || !closest || !grad_dist || !grad_points) return DPF_EINVAL;
+    const size_t n = (size_t)B * (size_t)N, per = (size_t)PM_MAX_BLOCKS * PM_THREADS;
+    for (size_t i0 = 0; i0 < n; i0 += per) {
+        const size_t cnt = n - i0 < per ? n - i0 : per;
+        hipLaunchKernelGGL(pm_grad_kernel, dim3((unsigned)((cnt + PM_THREADS - 1) / PM_THREADS)), dim3(PM_THREADS), 0, (hipStream_t)stream,
+                           i0, n, points, closest, grad_dist, grad_points);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    }
+    return 0;
+}

@@ -1,0 +1,1 @@
+from .point_mesh import point_mesh_distance, surface_accuracy   # noqa: F401

@@ -767,6 +767,53 @@ int dpf_mesh_sample(int M, const float *vertices, const long *vertex_bounds, con
                     const float *s2, int split, int xform, float shift_x, float shift_y, float shift_z, float scale,
                     float *cloud, float *eval_cloud, int *faces_out, dpf_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * Point-to-mesh distance over the same mesh store (csrc/point_mesh.hip): the exact squared distance from every query point to
+ * the surface it is measured against.  points (B, N, 3) fp32, point-major; slot b queries mesh mesh_idx[b] (int32, device);
+ * vertices / vertex_bounds / faces / face_bounds / flags are the arrays dpf_mesh_sample takes (flags as dpf_mesh_cdf_build
+ * left them).  Outputs: dist (B, N) fp32 = min over the mesh's faces of the squared distance to the closed triangle; face
+ * (B, N) int32 = the mesh-local index of a face attaining it; closest (B, N, 3) fp32, optional (NULL: not written) = the
+ * closest point on that face.
+ *   The arithmetic of one (point p, face (a, b, c)) pair is ONE fp32 sequence, the same in every kernel form; fma(x, y, z) is
+ *   the fused operation, dot(x, y) = fma(x2, y2, fma(x1, y1, x0 * y0)), everything else rounds on its own.
+ *   Per face: ab = b - a, ac = c - a, aa = dot(ab, ab), g = dot(ab, ac), cc = dot(ac, ac), bb = dot(ac - ab, ac - ab),
+ *     det = fma(aa, cc, -(g * g)); iaa = aa > 0 ? 1 / aa : 0, icc and ibc likewise from cc and bb (correctly rounded divisions);
+ *     the face is THIN when !(det > 2^-14 * (aa * cc)), else idet = 1 / det.
+ *   Per pair: ap = p - a, d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = d1 - aa, d4 = d2 - g, d5 = d1 - g, d6 = d2 - cc,
+ *     tab = clamp01(d1 * iaa), tac = clamp01(d2 * icc), tbc = clamp01((d4 - d3) * ibc)  (clamp01(x) = min(max(x, 0), 1), NaN -> 0).
+ *     Ericson's regions (Real-Time Collision Detection 5.1.5), first match: corner A (d1 <= 0 and d2 <= 0): (v, w) = (0, 0);
+ *     corner B (d3 >= 0 and d4 <= d3): (1, 0); edge AB (vc <= 0, d1 >= 0, d3 <= 0): (tab, 0); corner C (d6 >= 0 and d5 <= d6):
+ *     (0, 1); edge AC (vb <= 0, d2 >= 0, d6 <= 0): (0, tac); edge BC (v0 + w0 >= 1, d4 - d3 >= 0, d5 - d6 >= 0): (1 - tbc, tbc);
+ *     else the interior (v0, w0) -- with vb = fma(cc, d1, -(g * d2)), vc = fma(aa, d2, -(g * d1)), v0 = vb * idet, w0 = vc * idet.
+ *     Then v = clamp01(v), w = min(max(w, 0), 1 - v); q = fma(w, ac, fma(v, ab, a)) per axis; dist = dot(p - q, p - q).
+ *     No division per pair.  A THIN face -- zero area, repeated vertices, or a sliver whose determinant is mostly rounding -- is
+ *     the nearest of its three edges instead: (tab, 0), then (0, tac), then (1 - tbc, tbc), a later one only if strictly nearer;
+ *     an edge without length is its point.  No face yields NaN for finite input.  (A sliver just above the threshold carries the
+ *     interior solve's conditioning, a relative error of about 2^-23 / (det / (aa * cc)) in (v, w); DESIGN.md.)
+ *   Ties: among faces of equal fp32 distance the LOWEST index is reported -- the minimum of (distance bits << 32 | face) as
+ *     unsigned 64-bit keys.  dist, face and closest are bit-identical from run to run, do not depend on B, on the slot a cloud
+ *     sits in or on how faces and points are spread over workgroups and launches, and are the same in both kernel forms.
+ *   A slot whose mesh index is outside [0, M) or whose mesh is flagged reads nothing of the mesh: dist NaN, face -1, closest NaN.
+ *     A non-finite query point gives NaN / -1 for that point alone.  (Finite coordinates whose squares overflow fp32 are outside
+ *     the contract.)  A face index >= V_m flags its mesh in dpf_mesh_cdf_build, so no vertex outside the mesh is ever read.
+ *   max_faces: the largest face count among the meshes queried (host knowledge, >= 1) -- it only sizes the launch; a wrong
+ *     value costs time, never correctness.  form: 0 = by size (dispatch.h: pm_form), 1 = every workgroup walks all faces of its
+ *     slot's mesh in tiles of dpf_point_mesh_tile() faces, 2 = the tiles are also split over workgroups, merged by a 64-bit
+ *     atomic minimum into workspace (dpf_point_mesh_workspace_bytes(B, N) bytes, 8-byte aligned; only read or written when the
+ *     split form runs) and unpacked by a finishing launch.
+ *   Launches on the caller's stream, never synchronises, no memset nodes; B = 0 or N = 0 launches nothing; B and N are chunked
+ *     over launches.
+ *   dpf_point_mesh_distance_grad: grad_points (B, N, 3) = 2 * grad_dist * (points - closest), one launch; 0 where closest is NaN
+ *     (the points whose dist is NaN).  The mesh is data: there is no gradient with respect to vertices. */
+int dpf_point_mesh_tile(void);
+size_t dpf_point_mesh_workspace_bytes(int B, int N);
+int dpf_point_mesh_distance(int M, const float *vertices, const long *vertex_bounds, const unsigned int *faces,
+                            const long *face_bounds, const unsigned int *flags, int B, int N, const float *points,
+                            const int *mesh_idx, long max_faces, int form, float *dist, int *face, float *closest,
+                            void *workspace, size_t workspace_bytes, dpf_stream_t stream);
+int dpf_point_mesh_distance_grad(int B, int N, const float *points, const float *closest, const float *grad_dist,
+                                 float *grad_points, dpf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
