@@ -219,7 +219,10 @@ def run_frozen_stack(stack, spec, p, g, mode, precision=None):
     if g.shape[1] != spec.G:
         raise RuntimeError("g has %d features, the layers expect %d" % (g.shape[1], spec.G))
     with torch.cuda.device(p.device):
-        if spec.flat is not None and spec.flat.attached():
+        # the flat node adds to flat_g whatever requires grad (its token always does): with every parameter frozen (latent
+        # optimisation over a flattened decoder) the per-parameter node is taken, which forms no parameter gradient -- flat_g and
+        # grad_written stay as they are, as in the prior flow (prior_flows._frozen_prior)
+        if spec.flat is not None and spec.flat.attached() and any(t.requires_grad for t in spec.flat.params):
             outs = _FlowStackFrozenFlat.apply(p, g, spec.flat.token, stack, spec, mode, precision)
         else:
             outs = _FlowStackFrozen.apply(p, g, stack, spec, mode, precision, *spec.all_params())
