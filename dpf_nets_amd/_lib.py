@@ -123,6 +123,10 @@ SIGNATURES = {
     "dpf_point_mesh_workspace_bytes": (_sz, [_i, _i]),
     "dpf_point_mesh_distance": (_i, [_i] + [_vp] * 5 + [_i, _i, _vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dpf_point_mesh_distance_grad": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dpf_mesh_point_tile": (_i, []),
+    "dpf_mesh_point_workspace_bytes": (_sz, [_i, _l]),
+    "dpf_mesh_point_distance": (_i, [_i] + [_vp] * 5 + [_i, _i, _vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dpf_mesh_point_distance_grad": (_i, [_i, _i, _l, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dpf_version": (ctypes.c_char_p, []),
 }
 

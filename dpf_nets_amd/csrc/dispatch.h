@@ -289,5 +289,25 @@ inline PMForm pm_form(int b, int n, long max_faces, int force) {
     return {PMKernel::Split, (int)splits};
 }
 
+// ---- mesh-to-cloud distance (mesh_point.hip) --------------------------------------------------------------------------------
+constexpr int MP_WG_FACES = 256;    // faces of a workgroup: 4 waves, one staged face per lane
+constexpr int MP_TILE = 256;        // points per LDS tile (4 KB)
+constexpr int MP_MAX_SPLITS = 1024;
+// The roles of pm_form's arguments swapped.  Whole: every workgroup walks all point tiles of its slot.  Split: the point tiles are
+// dealt round-robin to `splits` workgroups per 256 faces (64-bit atomic minimum, then a finishing launch) -- where
+// b * ceil(max_faces / 256) workgroups leave CUs idle, as many splits as bring the launch to PM_FILL_WGS workgroups, never more
+// than the clouds have point tiles.  force: 0 by size, 1 Whole, 2 Split (with the splits the sizes ask for, at least one).
+// Total: any arguments give a form with 1 <= splits <= MP_MAX_SPLITS.
+inline PMForm mp_form(int b, int n, long max_faces, int force) {
+    const long chunks = max_faces > 0 ? ceil_div(max_faces, MP_WG_FACES) : 1;
+    const long slots = b > 0 ? (long)b : 1;
+    const long tiles = n > 0 ? ceil_div(n, MP_TILE) : 1;
+    long splits = chunks >= PM_FILL_WGS || slots * chunks >= PM_FILL_WGS ? 1 : ceil_div(PM_FILL_WGS, slots * chunks);
+    if (splits > tiles) splits = tiles;
+    if (splits > MP_MAX_SPLITS) splits = MP_MAX_SPLITS;
+    if (force == 1 || (force != 2 && splits < 2)) return {PMKernel::Whole, 1};
+    return {PMKernel::Split, (int)splits};
+}
+
 }  // namespace dispatch
 #endif  // DPF_DISPATCH_H

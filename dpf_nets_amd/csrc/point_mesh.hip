@@ -2,7 +2,7 @@
 // point the minimum over the faces of its slot's mesh of the squared distance to the closed triangle, a face that attains it
 // and the closest point on that face.  Brute force, B * N * F point-triangle tests, the faces broadcast from LDS.
 //
-// The contract is in include/dpf_hip.h; in short
+// The contract is in include/dpf_hip.h; the arithmetic of a pair lives in pm_pair.h, shared with mesh_point.hip.  In short
 //   pm_stage -- per face, once per tile and workgroup: 16 floats every lane of a wave shares (corner a, the edge vectors
 //               ab = b - a and ac = c - a, their dot products aa, g = ab.ac, cc, and the reciprocals 1/aa, 1/cc, 1/|c - b|^2,
 //               1/det with det = aa * cc - g * g).  A face is THIN when !(det > 2^-14 * (aa * cc)): degenerate faces (zero area,
@@ -27,122 +27,18 @@
 
 #include "dpf_hip.h"
 #include "dispatch.h"
+#include "pm_pair.h"
 
 namespace {
+
+using namespace pm;                                 // PMStore, PMFace, pm_stage, pm_eval, pm_slot, ...: the pair arithmetic (pm_pair.h)
 
 constexpr int PM_THREADS = dispatch::PM_WG_POINTS;  // threads = points of a workgroup: one point per lane, 4 waves
 constexpr int PM_TILE = dispatch::PM_TILE;          // faces per LDS tile: one face staged per thread
 constexpr int PM_MAX_SLOTS = 32768;                 // batch slots per launch (grid.y)
 constexpr long PM_MAX_BLOCKS = 1L << 22;            // point chunks per launch (grid.x)
-constexpr float PM_THIN = 6.103515625e-05f;         // 2^-14
 
 static_assert(PM_TILE == PM_THREADS, "one thread stages one face of a tile");
-
-struct PMStore {
-    int M;
-    const float *vertices;
-    const long *vertex_bounds;
-    const unsigned int *faces;
-    const long *face_bounds;
-    const unsigned int *flags;
-};
-
-// what the lanes of a wave share about a face
-struct PMFace {
-    float ax, ay, az, aa;
-    float abx, aby, abz, g;
-    float acx, acy, acz, cc;
-    float iaa, icc, ibc, idet;
-};
-
-__device__ __forceinline__ float pm_dot(float ax, float ay, float az, float bx, float by, float bz) {
-    return fmaf(az, bz, fmaf(ay, by, ax * bx));
-}
-
-__device__ __forceinline__ PMFace pm_stage(const float *v0, const float *v1, const float *v2) {
-    PMFace f;
-    f.ax = v0[0]; f.ay = v0[1]; f.az = v0[2];
-    f.abx = v1[0] - f.ax; f.aby = v1[1] - f.ay; f.abz = v1[2] - f.az;
-    f.acx = v2[0] - f.ax; f.acy = v2[1] - f.ay; f.acz = v2[2] - f.az;
-    f.aa = pm_dot(f.abx, f.aby, f.abz, f.abx, f.aby, f.abz);
-    f.g = pm_dot(f.abx, f.aby, f.abz, f.acx, f.acy, f.acz);
-    f.cc = pm_dot(f.acx, f.acy, f.acz, f.acx, f.acy, f.acz);
-    const float ex = f.acx - f.abx, ey = f.acy - f.aby, ez = f.acz - f.abz;
-    const float bb = pm_dot(ex, ey, ez, ex, ey, ez);
-    const float det = fmaf(f.aa, f.cc, -(f.g * f.g));
-    f.iaa = f.aa > 0.0f ? 1.0f / f.aa : 0.0f;
-    f.icc = f.cc > 0.0f ? 1.0f / f.cc : 0.0f;
-    f.ibc = bb > 0.0f ? 1.0f / bb : 0.0f;
-    f.idet = det > PM_THIN * (f.aa * f.cc) ? 1.0f / det : 0.0f;
-    return f;
-}
-
-__device__ __forceinline__ float pm_clamp01(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }     // (a NaN becomes 0)
-
-// q = a + v * ab + w * ac and |p - q|^2
-__device__ __forceinline__ float pm_point(const PMFace &f, float px, float py, float pz, float v, float w, float &qx, float &qy,
-                                          float &qz) {
-    qx = fmaf(w, f.acx, fmaf(v, f.abx, f.ax));
-    qy = fmaf(w, f.acy, fmaf(v, f.aby, f.ay));
-    qz = fmaf(w, f.acz, fmaf(v, f.abz, f.az));
-    const float dx = px - qx, dy = py - qy, dz = pz - qz;
-    return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-}
-
-__device__ __forceinline__ float pm_eval(const PMFace &f, float px, float py, float pz, float &qx, float &qy, float &qz) {
-    const float apx = px - f.ax, apy = py - f.ay, apz = pz - f.az;
-    const float d1 = pm_dot(f.abx, f.aby, f.abz, apx, apy, apz), d2 = pm_dot(f.acx, f.acy, f.acz, apx, apy, apz);
-    const float d3 = d1 - f.aa, d4 = d2 - f.g, d5 = d1 - f.g, d6 = d2 - f.cc;
-    const float tab = pm_clamp01(d1 * f.iaa), tac = pm_clamp01(d2 * f.icc), tbc = pm_clamp01((d4 - d3) * f.ibc);
-    if (f.idet == 0.0f) {                                                   // a thin face: the nearest of its three edges (the same for every lane)
-        float d = pm_point(f, px, py, pz, tab, 0.0f, qx, qy, qz);
-        float x, y, z;
-        float e = pm_point(f, px, py, pz, 0.0f, tac, x, y, z);
-        if (e < d) { d = e; qx = x; qy = y; qz = z; }
-        e = pm_point(f, px, py, pz, 1.0f - tbc, tbc, x, y, z);
-        if (e < d) { d = e; qx = x; qy = y; qz = z; }
-        return d;
-    }
-    const float vb = fmaf(f.cc, d1, -(f.g * d2)), vc = fmaf(f.aa, d2, -(f.g * d1));
-    float v = vb * f.idet, w = vc * f.idet;                                // inside the triangle
-    bool c = v + w >= 1.0f && d4 - d3 >= 0.0f && d5 - d6 >= 0.0f;           // edge BC (va <= 0)
-    v = c ? 1.0f - tbc : v; w = c ? tbc : w;
-    c = vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f;                             // edge AC
-    v = c ? 0.0f : v; w = c ? tac : w;
-    c = d6 >= 0.0f && d5 <= d6;                                             // corner C
-    v = c ? 0.0f : v; w = c ? 1.0f : w;
-    c = vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f;                             // edge AB
-    v = c ? tab : v; w = c ? 0.0f : w;
-    c = d3 >= 0.0f && d4 <= d3;                                             // corner B
-    v = c ? 1.0f : v; w = c ? 0.0f : w;
-    c = d1 <= 0.0f && d2 <= 0.0f;                                           // corner A
-    v = c ? 0.0f : v; w = c ? 0.0f : w;
-    v = pm_clamp01(v);                                                      // whatever rounding did to the classification,
-    w = fminf(fmaxf(w, 0.0f), 1.0f - v);                                    // q lies on the closed triangle
-    return pm_point(f, px, py, pz, v, w, qx, qy, qz);
-}
-
-struct PMSlot { bool ok; long fb, vb; int F; };
-
-__device__ __forceinline__ PMSlot pm_slot(const PMStore &st, const int *mesh_idx, size_t b) {
-    PMSlot s{false, 0, 0, 0};
-    const int m = mesh_idx[b];
-    if (m < 0 || m >= st.M || st.flags[m] != 0u) return s;                  // nothing of such a mesh is read
-    s.fb = st.face_bounds[m]; s.vb = st.vertex_bounds[m];
-    s.F = (int)(st.face_bounds[m + 1] - s.fb);
-    s.ok = s.F >= 1;
-    return s;
-}
-
-__device__ __forceinline__ PMFace pm_stage_face(const PMStore &st, const PMSlot &s, int face) {
-    const unsigned int *fi = st.faces + (size_t)(s.fb + face) * 3;          // validated by dpf_mesh_cdf_build: flags[m] == 0
-    return pm_stage(st.vertices + (size_t)(s.vb + fi[0]) * 3, st.vertices + (size_t)(s.vb + fi[1]) * 3,
-                    st.vertices + (size_t)(s.vb + fi[2]) * 3);
-}
-
-__device__ __forceinline__ bool pm_finite(float x, float y, float z) {
-    return fabsf(x) <= 3.402823466e38f && fabsf(y) <= 3.402823466e38f && fabsf(z) <= 3.402823466e38f;   // (false for NaN)
-}
 
 // the outputs of one point from its key
 __device__ __forceinline__ void pm_write(const PMStore &st, const PMSlot &s, bool finite, unsigned long long key, float px, float py,

@@ -5,6 +5,13 @@ of a target cloud -- as a metric and as a loss with a gradient with respect to t
   point_mesh_distance -- dist (B, N), face (B, N)[, closest (B, N, 3)]
   surface_accuracy    -- dist.mean(1) (B,)[, the percentage of points nearer than a threshold]
 
+and the other direction (csrc/mesh_point.hip), per face of the mesh the nearest point of the cloud -- what the prediction left
+uncovered:
+
+  mesh_point_distance  -- dist (B, W), point (B, W)[, closest (B, W, 3)][, area (B, W)]
+  surface_completeness -- the area-weighted mean of dist over each mesh's faces (B,)[, the weighted percentage of faces reached]
+  surface_chamfer      -- surface_accuracy + surface_completeness (B,)
+
 The mesh is data: no gradient flows to its vertices.  The arithmetic and the tie rule are in include/dpf_hip.h."""
 import numpy as np
 import torch
@@ -12,7 +19,7 @@ import torch
 from .._lib import lib, check, current_stream
 from ..datasets.sampling import MeshStore, CloudTransform
 
-__all__ = ["point_mesh_distance", "surface_accuracy"]
+__all__ = ["point_mesh_distance", "surface_accuracy", "mesh_point_distance", "surface_completeness", "surface_chamfer"]
 
 
 def _store_args(store):
@@ -115,6 +122,59 @@ def _frame(store, transform, slots):
     return mask, os_, oc, torch.from_numpy(np.asarray(shift, np.float32)).to(store.device), float(scale)
 
 
+def _checked(name, points, store, form):
+    if not isinstance(store, MeshStore):
+        raise RuntimeError("%s: store must be a datasets.MeshStore" % name)
+    if not isinstance(points, torch.Tensor) or not points.is_cuda:
+        raise RuntimeError("%s needs a CUDA tensor of points (there is no CPU fallback)" % name)
+    if points.dtype != torch.float32:
+        raise RuntimeError("%s: points must be float32, got %s" % (name, points.dtype))
+    if points.dim() != 3 or points.shape[2] != 3:
+        raise RuntimeError("%s: points must be (B, N, 3), got %s" % (name, tuple(points.shape)))
+    if points.device != store.device:
+        raise RuntimeError("%s: points are on %s, the store on %s" % (name, points.device, store.device))
+    if not points.is_contiguous():
+        raise RuntimeError("%s: points must be contiguous (point-major, as nn_distance takes them)" % name)
+    if form not in (0, 1, 2):
+        raise RuntimeError("%s: form must be 0, 1 or 2" % name)
+
+
+def _to_mesh_frame(points, store, transform, slots):
+    """(the points mapped back into the meshes' frame by the transform's inverse steps, the factor (B, 1) or None that takes
+    squared lengths of that frame to the clouds', the frame for _to_cloud_frame)"""
+    if transform is None:
+        return points, None, None
+    mask, os_, oc, shift, scale = frame = _frame(store, transform, slots)
+    local, factor = points, None
+    if mask & 8:
+        local = local * scale
+    if mask & 4:
+        local = local + shift
+    if mask & 2:
+        local = local - oc
+    if mask & 1:
+        local = local / os_
+    if mask & 9:                                                                       # dist' = dist * (orig_s / scale)^2
+        factor = (os_.view(-1, 1) if mask & 1 else 1.0) / (scale if mask & 8 else 1.0)
+        factor = factor * factor
+    return local.contiguous(), factor, frame
+
+
+def _to_cloud_frame(closest, frame):
+    if frame is None:
+        return closest
+    mask, os_, oc, shift, scale = frame
+    if mask & 1:
+        closest = closest * os_
+    if mask & 2:
+        closest = closest + oc
+    if mask & 4:
+        closest = closest - shift
+    if mask & 8:
+        closest = closest / scale
+    return closest
+
+
 def point_mesh_distance(points, store, mesh_indices, return_closest=False, transform=None, form=0):
     """dist (B, N) float32: the squared distance from points[b, i] to the nearest point of mesh mesh_indices[b] of `store`;
     face (B, N) int32: a face of that mesh attaining it (the lowest index among equals); with return_closest also closest
@@ -135,51 +195,15 @@ def point_mesh_distance(points, store, mesh_indices, return_closest=False, trans
     raises: those cannot be undone from the cloud alone.
 
     form: 0 lets csrc/dispatch.h choose the kernel form; 1 / 2 force one (tests)."""
-    if not isinstance(store, MeshStore):
-        raise RuntimeError("point_mesh_distance: store must be a datasets.MeshStore")
-    if not isinstance(points, torch.Tensor) or not points.is_cuda:
-        raise RuntimeError("point_mesh_distance needs a CUDA tensor of points (there is no CPU fallback)")
-    if points.dtype != torch.float32:
-        raise RuntimeError("point_mesh_distance: points must be float32, got %s" % points.dtype)
-    if points.dim() != 3 or points.shape[2] != 3:
-        raise RuntimeError("point_mesh_distance: points must be (B, N, 3), got %s" % (tuple(points.shape),))
-    if points.device != store.device:
-        raise RuntimeError("point_mesh_distance: points are on %s, the store on %s" % (points.device, store.device))
-    if not points.is_contiguous():
-        raise RuntimeError("point_mesh_distance: points must be contiguous (point-major, as nn_distance takes them)")
-    if form not in (0, 1, 2):
-        raise RuntimeError("point_mesh_distance: form must be 0, 1 or 2")
+    _checked("point_mesh_distance", points, store, form)
     slots, most = _slots(mesh_indices, store, int(points.shape[0]))
-    local, factor = points, None
-    if transform is not None:
-        mask, os_, oc, shift, scale = _frame(store, transform, slots)
-        if mask & 8:
-            local = local * scale
-        if mask & 4:
-            local = local + shift
-        if mask & 2:
-            local = local - oc
-        if mask & 1:
-            local = local / os_
-        if mask & 9:                                                                   # dist' = dist * (orig_s / scale)^2
-            factor = (os_.view(-1, 1) if mask & 1 else 1.0) / (scale if mask & 8 else 1.0)
-            factor = factor * factor
-        local = local.contiguous()
+    local, factor, frame = _to_mesh_frame(points, store, transform, slots)
     dist, face, closest = _PointMeshDistance.apply(local, store, slots, most, int(form), bool(return_closest))
     if factor is not None:
         dist = dist * factor
     if not return_closest:
         return dist, face
-    if transform is not None:
-        if mask & 1:
-            closest = closest * os_
-        if mask & 2:
-            closest = closest + oc
-        if mask & 4:
-            closest = closest - shift
-        if mask & 8:
-            closest = closest / scale
-    return dist, face, closest
+    return dist, face, _to_cloud_frame(closest, frame)
 
 
 def surface_accuracy(points, store, mesh_indices, threshold=None, transform=None):
@@ -190,3 +214,123 @@ def surface_accuracy(points, store, mesh_indices, threshold=None, transform=None
     if threshold is None:
         return dist.mean(1)
     return dist.mean(1), 100.0 * (dist < threshold).to(dist.dtype).mean(1)
+
+
+# ---- the other direction: per face the nearest point ----------------------------------------------------------------------------
+def _launch_faces(points, store, slots, width, form, want_closest, want_area):
+    B, N = int(points.shape[0]), int(points.shape[1])
+    dev = points.device
+    dist = torch.empty((B, width), dtype=torch.float32, device=dev)
+    point = torch.empty((B, width), dtype=torch.int32, device=dev)
+    closest = torch.empty((B, width, 3), dtype=torch.float32, device=dev) if want_closest else None
+    area = torch.empty((B, width), dtype=torch.float32, device=dev) if want_area else None
+    if B and width:
+        L = lib()
+        with torch.cuda.device(dev):
+            nbytes = L.dpf_mesh_point_workspace_bytes(B, width)
+            ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
+            check(L.dpf_mesh_point_distance(*_store_args(store), B, N, points.data_ptr() if N else None, slots.data_ptr(), width, form,
+                                            dist.data_ptr(), point.data_ptr(), None if closest is None else closest.data_ptr(),
+                                            None if area is None else area.data_ptr(), ws.data_ptr(), nbytes, current_stream()),
+                  "mesh_point_distance")
+    return dist, point, closest, area
+
+
+class _MeshPointDistance(torch.autograd.Function):
+    """One node: the forward search saves the nearest points' indices and the closest points on the faces, the backward is one
+    launch that gathers 2 * g * (p - closest) per point in face order."""
+
+    @staticmethod
+    def forward(ctx, points, store, slots, width, form, return_closest, return_area):
+        wants_grad = bool(ctx.needs_input_grad[0])
+        dist, point, closest, area = _launch_faces(points, store, slots, width, form, bool(return_closest) or wants_grad, bool(return_area))
+        if wants_grad:
+            ctx.save_for_backward(points, point, closest)
+        if closest is None:
+            closest = points.new_empty((0,))
+        if area is None:
+            area = points.new_empty((0,))
+        ctx.mark_non_differentiable(point, closest, area)
+        return dist, point, closest, area
+
+    @staticmethod
+    def backward(ctx, grad_dist, _grad_point, _grad_closest, _grad_area):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 7
+        points, point, closest = ctx.saved_tensors
+        B, N, W = int(points.shape[0]), int(points.shape[1]), int(point.shape[1])
+        grad = torch.empty_like(points)
+        if B and N:
+            g = grad_dist.contiguous()
+            with torch.cuda.device(points.device):
+                check(lib().dpf_mesh_point_distance_grad(B, N, W, points.data_ptr(), point.data_ptr(), closest.data_ptr(), g.data_ptr(),
+                                                         grad.data_ptr(), current_stream()), "mesh_point_distance_grad")
+        return (grad,) + (None,) * 6
+
+
+def mesh_point_distance(points, store, mesh_indices, return_closest=False, return_area=False, transform=None, form=0):
+    """The other direction of point_mesh_distance: for every face of mesh mesh_indices[b] the nearest of cloud b's points.
+    dist (B, W) float32: the smallest squared distance from a point of the cloud to the closed triangle; point (B, W) int32: the
+    index of a point attaining it (the lowest among equals); with return_closest also closest (B, W, 3): the point of the face
+    nearest to that point; with return_area also area (B, W): the face's area as the store's sampler forms it.  W is the largest
+    face count among the meshes asked for (of the store, when mesh_indices is a device tensor).  Arguments and refusals as
+    point_mesh_distance: anything but a contiguous float32 (B, N, 3) CUDA tensor on the store's device raises RuntimeError --
+    there is no CPU path.
+
+    Columns past a mesh's own face count, and every column of a slot whose mesh index is outside the store, whose mesh is
+    flagged or whose cloud has no finite point (N = 0 included), hold dist NaN, point -1, closest NaN, area 0.  A non-finite
+    point is skipped.  The results are bit-identical from run to run and do not depend on the batch or the form.
+
+    Autograd: one node.  d dist[b, f] / d points[b, point[b, f]] = 2 * (point - closest), gathered per point over the faces that
+    name it in face order -- one launch in the backward, no atomics, and none unless points needs a gradient.  A point no face
+    names gets 0.  point, closest and area carry no gradient, and the mesh is data: nothing flows to its vertices.
+
+    transform: as in point_mesh_distance -- the points are mapped back by the inverse steps; dist and area are returned in the
+    clouds' frame, dist' = dist * (orig_s / scale)^2 and area likewise, closest in the clouds' frame too.  A transform with noise
+    or centring raises.
+
+    form: 0 lets csrc/dispatch.h choose the kernel form; 1 / 2 force one (tests)."""
+    _checked("mesh_point_distance", points, store, form)
+    slots, width = _slots(mesh_indices, store, int(points.shape[0]))
+    local, factor, frame = _to_mesh_frame(points, store, transform, slots)
+    dist, point, closest, area = _MeshPointDistance.apply(local, store, slots, width, int(form), bool(return_closest), bool(return_area))
+    if factor is not None:
+        dist = dist * factor
+        if return_area:
+            area = area * factor
+    out = (dist, point)
+    if return_closest:
+        out += (_to_cloud_frame(closest, frame),)
+    if return_area:
+        out += (area,)
+    return out
+
+
+def surface_completeness(points, store, mesh_indices, threshold=None, transform=None, weights="area"):
+    """(B,) weighted mean over each mesh's faces of the squared distance from the face to the nearest point of its cloud: the
+    surface-to-predicted half of Chamfer, which sees the geometry a cloud leaves uncovered (a cloud collapsed onto one corner
+    scores a perfect surface_accuracy and a poor completeness).  weights: "area" -- each face's area over its mesh's total --
+    or "uniform" -- 1 / F_b.  With `threshold` also the (B,) weighted percentage of faces with dist < threshold.  A bad slot (see
+    mesh_point_distance) gives NaN.  Arguments as mesh_point_distance; differentiable with respect to points through it.
+
+    What the number is: a face counts as reached when ONE point is near ANY part of it, so this is a lower bound on the
+    surface-to-cloud distance an integral over the surface would give.  It is sharp for meshes whose faces are small against the
+    spacing of the points and loose for a table top made of two triangles, which a single point on its diagonal covers.  For a
+    sampled estimate of the integral use datasets.sample_clouds + nn_distance."""
+    if weights not in ("area", "uniform"):
+        raise RuntimeError("surface_completeness: weights must be 'area' or 'uniform'")
+    dist, point, area = mesh_point_distance(points, store, mesh_indices, return_area=True, transform=transform)
+    real = point >= 0
+    w = area if weights == "area" else real.to(dist.dtype)
+    w = w / w.sum(1, keepdim=True)                                                     # (0 / 0 = NaN: a bad slot)
+    mean = (torch.where(real, dist, torch.zeros_like(dist)) * w).sum(1)
+    if threshold is None:
+        return mean
+    return mean, 100.0 * ((real & (dist < threshold)).to(dist.dtype) * w).sum(1)
+
+
+def surface_chamfer(points, store, mesh_indices, transform=None):
+    """(B,) surface_accuracy + surface_completeness: both directions of the squared distance between a cloud and the surface it
+    should lie on.  Arguments as point_mesh_distance; differentiable with respect to points."""
+    return surface_accuracy(points, store, mesh_indices, transform=transform) + surface_completeness(points, store, mesh_indices,
+                                                                                                       transform=transform)

@@ -814,6 +814,44 @@ int dpf_point_mesh_distance(int M, const float *vertices, const long *vertex_bou
 int dpf_point_mesh_distance_grad(int B, int N, const float *points, const float *closest, const float *grad_dist,
                                  float *grad_points, dpf_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * Mesh-to-cloud distance over the same mesh store (csrc/mesh_point.hip): the other direction -- for every FACE of a slot's mesh
+ * the nearest of the slot's points; the column minimum of the (point, face) matrix whose row minimum dpf_point_mesh_distance
+ * returns.  Store arrays, points (B, N, 3), mesh_idx (B), max_faces, form, workspace and stream as there.  W = max_faces is the
+ * width of the outputs: dist (B, W) fp32 = for face f of slot b's mesh the minimum over that slot's points of the pair's squared
+ * distance; point (B, W) int32 = the index of a point attaining it; closest (B, W, 3) fp32, optional (NULL: not written) = the
+ * closest point on the face to that point; area (B, W) fp32, optional = the face's area.
+ *   Pair arithmetic: the sequence stated above, defined once (csrc/pm_pair.h) and included by both translation units; a pair has
+ *     the same bits in both directions.
+ *   Area: dpf_mesh_cdf_build's fp32 sequence (e1 = p2 - p0, e2 = p2 - p1, cross product as a product minus a product,
+ *     sqrt((c0*c0 + c1*c1) + c2*c2) / 2, nothing fused), 0 where that build counts the face as 0 (a non-finite area).
+ *   Ties: among points of equal fp32 distance the LOWEST point index is reported -- the minimum of (distance bits << 32 | point
+ *     index) as unsigned 64-bit keys.  A non-finite point is skipped: it is never a face's nearest.
+ *   Bad slots: dist NaN, point -1, closest NaN, area 0 in all W columns when the mesh index is outside [0, M), the mesh is
+ *     flagged, or no point of the slot is finite (N = 0 included).  Nothing of the mesh is read in the first two cases.
+ *   Padding: columns f >= F_b of any slot are NaN / -1 / NaN / 0 too, and nothing of a mesh is read for them.  (With max_faces
+ *     below a mesh's face count only its first W faces are answered.)
+ *   dist, point, closest and area are bit-identical from run to run and do not depend on B, on the slot, on how faces and points
+ *     are spread over workgroups and launches, or on the form.
+ *   form: 0 = by size (dispatch.h: mp_form), 1 = a workgroup holds dpf_mesh_point_tile() faces, one per lane, and walks all of
+ *     its slot's points in tiles of as many, 2 = the point tiles are also split over workgroups, merged by a 64-bit atomic minimum
+ *     into workspace (dpf_mesh_point_workspace_bytes(B, max_faces) bytes, 8-byte aligned; only read or written when the split
+ *     form runs) and unpacked by a finishing launch.
+ *   Launches on the caller's stream, never synchronises, no memset nodes; B = 0 or max_faces = 0 launches nothing; B and the
+ *     faces are chunked over launches.  max_faces < 2^31.
+ *   dpf_mesh_point_distance_grad: grad_points (B, N, 3)[i] = the sum over the faces f with point[b, f] == i, in ascending f, of
+ *     2 * grad_dist[b, f] * (points[b, i] - closest[b, f]) -- each term (2 * g) * (p - q) rounded on its own and added to a sum
+ *     that starts at 0; a component whose closest is NaN adds 0; a point no face names gets 0.  A gather, one launch, no
+ *     floating-point atomics: bit-identical from run to run.  The mesh is data: there is no gradient with respect to vertices. */
+int dpf_mesh_point_tile(void);
+size_t dpf_mesh_point_workspace_bytes(int B, long max_faces);
+int dpf_mesh_point_distance(int M, const float *vertices, const long *vertex_bounds, const unsigned int *faces,
+                            const long *face_bounds, const unsigned int *flags, int B, int N, const float *points,
+                            const int *mesh_idx, long max_faces, int form, float *dist, int *point, float *closest, float *area,
+                            void *workspace, size_t workspace_bytes, dpf_stream_t stream);
+int dpf_mesh_point_distance_grad(int B, int N, long max_faces, const float *points, const int *point, const float *closest,
+                                 const float *grad_dist, float *grad_points, dpf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
