@@ -127,6 +127,11 @@ SIGNATURES = {
     "dpf_mesh_point_workspace_bytes": (_sz, [_i, _l]),
     "dpf_mesh_point_distance": (_i, [_i] + [_vp] * 5 + [_i, _i, _vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dpf_mesh_point_distance_grad": (_i, [_i, _i, _l, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dpf_emd_exact_max_points": (_i, []),
+    "dpf_emd_exact_workspace_bytes": (_sz, [_l, _i]),
+    "dpf_emd_exact": (_i, [_i, _i, _vp, _l, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dpf_pairwise_emd_exact": (_i, [_i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dpf_emd_exact_grad": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dpf_version": (ctypes.c_char_p, []),
 }
 

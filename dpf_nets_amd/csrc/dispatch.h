@@ -309,5 +309,25 @@ inline PMForm mp_form(int b, int n, long max_faces, int force) {
     return {PMKernel::Split, (int)splits};
 }
 
+// ---- exact EMD (emd_exact.hip) ------------------------------------------------------------------------------------------------
+constexpr int EE_MAX_POINTS = 8192;     // points per cloud: the bidder tag of a bid key has 13 bits, the streamed form's LDS 128 KB
+constexpr int EE_LDS_POINTS = 4096;     // the resident form's: 36 bytes a point, 144 KB of the CU's 160
+constexpr int EE_MIN_BITS = 1, EE_MAX_BITS = 24;   // the cost grid's bits: rint(d * s) < 2^bits is an exact fp32 integer up to 24
+constexpr int EE_EPS0_SHIFT = 4;        // the first epsilon: ((n + 1) << bits) >> 4
+constexpr int EE_EPS_SHIFT = 3;         // epsilon falls by 3 bits a phase (oracle, Gaussian clouds of 2 048 points: 10 780 rounds against
+                                        // 27 114 at 2 bits and 25 865 at 1)
+// Resident: the second cloud and the bids in LDS; Streamed: the cloud read from global memory, the bids in the caller's workspace.
+// The resident form wherever it fits (it never waits on L2).  force: 0 by size, 1 Resident, 2 Streamed; Unserved: n outside
+// 1..EE_MAX_POINTS, or the resident form forced past EE_LDS_POINTS.  threads: a wave for clouds of up to 64 points (its barriers are
+// free), 4 waves up to 512, else 16 -- late rounds cut a lone bidder's candidates into slices of >= 64 for the idle waves.
+enum class EEKernel { Resident, Streamed, Unserved };
+struct EEForm { EEKernel kernel; int threads, lds_per_point; };
+inline EEForm ee_form(int n, int force) {
+    if (n < 1 || n > EE_MAX_POINTS || (force == 1 && n > EE_LDS_POINTS)) return {EEKernel::Unserved, 0, 0};
+    const int threads = n <= 64 ? 64 : n <= 512 ? 256 : 1024;
+    if (force == 2 || (force != 1 && n > EE_LDS_POINTS)) return {EEKernel::Streamed, threads, 16};
+    return {EEKernel::Resident, threads, 36};
+}
+
 }  // namespace dispatch
 #endif  // DPF_DISPATCH_H

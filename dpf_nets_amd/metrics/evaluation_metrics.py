@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from ..networks.utils import distChamferCUDA, emd_approx, chamfer_per_cloud, chamfer_cd_per_cloud  # noqa: F401
-from ..networks.utils import pairwise_CD, pairwise_EMD
+from ..networks.utils import pairwise_CD, pairwise_EMD, pairwise_EMD_exact, emd_exact  # noqa: F401
 from .._lib import lib, check, current_stream
 
 
@@ -117,25 +117,31 @@ def lgan_mmd_cov(all_dist):
     }
 
 
-def _pairwise_matrices(clouds1, clouds2, batch_size):
+def _pairwise_matrices(clouds1, clouds2, batch_size, emd="approx"):
     """(CD, EMD) matrices of every cloud of clouds1 against every cloud of clouds2: one matrix launch per chunk for each, both
-    sets read in place (what _pairwise_EMD_CD_ returns, without its per-row loop and without forming any matching)."""
-    return pairwise_CD(clouds1, clouds2, bs=batch_size), pairwise_EMD(clouds1, clouds2, bs=batch_size)
+    sets read in place (what _pairwise_EMD_CD_ returns, without its per-row loop and without forming any matching).
+    emd: "approx" -- pairwise_EMD, the reference's matcher; "exact" -- pairwise_EMD_exact, the optimal matching."""
+    if emd not in ("approx", "exact"):
+        raise ValueError("emd must be 'approx' or 'exact', got %r" % (emd,))
+    emd_matrix = pairwise_EMD if emd == "approx" else pairwise_EMD_exact
+    return pairwise_CD(clouds1, clouds2, bs=batch_size), emd_matrix(clouds1, clouds2, bs=batch_size)
 
 
-def compute_all_metrics(sample_pcs, ref_pcs, batch_size, accelerated_cd=False):
+def compute_all_metrics(sample_pcs, ref_pcs, batch_size, accelerated_cd=False, emd="approx"):
     """The generation metrics of the reference (:172-200): MMD and COV (lgan_mmd_cov) from the (sample, reference) matrices
     and 1-NN accuracy (knn, k = 1) from those plus the (reference, reference) and (sample, sample) matrices, for Chamfer and
     approximate EMD.  Keys "lgan_mmd-CD", "lgan_cov-CD", "lgan_mmd_smp-CD", the same for EMD, "1-NN-CD-acc_t",
     "1-NN-CD-acc_f", "1-NN-CD-acc" and the same for EMD.  The reference's orientation is kept: the cross matrices are computed
     as (reference, sample) and transposed for lgan_mmd_cov, and approx-EMD is not symmetric in its operands.  `batch_size`
-    bounds the pairs per launch; `accelerated_cd` is accepted and ignored (module docstring).  No autograd (pairwise_EMD)."""
+    bounds the pairs per launch; `accelerated_cd` is accepted and ignored (module docstring).  No autograd (pairwise_EMD).
+    emd="exact" builds the three EMD matrices from pairwise_EMD_exact (the optimal matching; same keys); the default is the
+    reference's approximate matcher."""
     results = {}
-    M_rs_cd, M_rs_emd = _pairwise_matrices(ref_pcs, sample_pcs, batch_size)
+    M_rs_cd, M_rs_emd = _pairwise_matrices(ref_pcs, sample_pcs, batch_size, emd)
     for metric, M in (("CD", M_rs_cd), ("EMD", M_rs_emd)):
         results.update({"%s-%s" % (k, metric): v for k, v in lgan_mmd_cov(M.t()).items()})
-    M_rr_cd, M_rr_emd = _pairwise_matrices(ref_pcs, ref_pcs, batch_size)
-    M_ss_cd, M_ss_emd = _pairwise_matrices(sample_pcs, sample_pcs, batch_size)
+    M_rr_cd, M_rr_emd = _pairwise_matrices(ref_pcs, ref_pcs, batch_size, emd)
+    M_ss_cd, M_ss_emd = _pairwise_matrices(sample_pcs, sample_pcs, batch_size, emd)
     for metric, (M_rr, M_rs, M_ss) in (("CD", (M_rr_cd, M_rs_cd, M_ss_cd)), ("EMD", (M_rr_emd, M_rs_emd, M_ss_emd))):
         results.update({"1-NN-%s-%s" % (metric, k): v for k, v in knn(M_rr, M_rs, M_ss, 1, sqrt=False).items() if 'acc' in k})
     return results

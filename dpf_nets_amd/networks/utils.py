@@ -259,6 +259,163 @@ def pairwise_EMD(clouds1, clouds2, bs=512, shard_rows=False):
     return emds
 
 
+EMD_EXACT_MAX_ROUNDS = 1 << 20      # rounds per pair over all phases: ~100 times what Gaussian clouds of 2 048 points need (10 780)
+EMD_EXACT_STATUS = {-1: "refused input (a non-finite coordinate or an extent whose square is not a normal float32)",
+                    -2: "round cap reached (max_rounds)", -3: "bid range exceeded"}
+
+
+def _emd_exact_check(x, name):
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[2] == 3 and x.is_contiguous()):
+        raise RuntimeError("emd_exact: %s must be a contiguous float32 CUDA tensor of shape (B, n, 3); there is no CPU path" % name)
+
+
+def _emd_exact_sizes(n, m, bits, max_rounds):
+    from .._lib import lib
+    if n != m:
+        raise RuntimeError("emd_exact needs clouds of equal size, got %d and %d points" % (n, m))
+    limit = lib().dpf_emd_exact_max_points()
+    if n > limit:
+        raise RuntimeError("emd_exact serves clouds of up to %d points, got %d" % (limit, n))
+    if not 1 <= int(bits) <= 24 or int(max_rounds) < 0 or int(max_rounds) > 0x7fffffff:
+        raise RuntimeError("emd_exact: bits must be in 1..24 and max_rounds in 0..2^31-1")
+
+
+def _emd_exact_warn(status, what):
+    """one RuntimeWarning naming the status of every unsolved pair (reads the statuses: a device synchronisation)"""
+    bad = status[status < 0]
+    if bad.numel():
+        import warnings
+        codes = sorted(set(bad.tolist()), reverse=True)
+        warnings.warn("%s: %d of %d pairs not solved and set to NaN -- %s" % (
+            what, bad.numel(), status.numel(), "; ".join("status %d: %s" % (c, EMD_EXACT_STATUS.get(c, "?")) for c in codes)),
+            RuntimeWarning, stacklevel=3)
+
+
+def _emd_exact_workspace(pairs, n, dev):
+    from .._lib import lib
+    nbytes = lib().dpf_emd_exact_workspace_bytes(pairs, n)
+    return torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev), nbytes
+
+
+class EMDExactFunction(torch.autograd.Function):
+    """cost (B,) of the optimal matching as ONE autograd node: forward = one dpf_emd_exact launch, the assignment and its inverse
+    kept for the backward, which is one dpf_emd_exact_grad launch for the inputs that need a gradient (the assignment is a constant,
+    as in the reference's match_cost backward)."""
+
+    @staticmethod
+    def forward(ctx, sample, ref, bits, max_rounds, form, normalise):
+        from .._lib import lib, check, current_stream
+        B, n = sample.shape[0], sample.shape[1]
+        dev = sample.device
+        assignment = torch.empty((B, n), dtype=torch.int32, device=dev)
+        inverse = torch.empty((B, n), dtype=torch.int32, device=dev)
+        qcost = torch.empty((B,), dtype=torch.int64, device=dev)
+        cost = torch.empty((B,), dtype=torch.float32, device=dev)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        if B > 0 and n > 0:
+            with torch.cuda.device(dev):
+                ws, nbytes = _emd_exact_workspace(B, n, dev)
+                check(lib().dpf_emd_exact(B, n, sample.data_ptr(), n * 3, ref.data_ptr(), n * 3, int(bits), int(max_rounds), int(form),
+                                          assignment.data_ptr(), inverse.data_ptr(), qcost.data_ptr(), cost.data_ptr(),
+                                          status.data_ptr(), ws.data_ptr(), nbytes, current_stream()), "emd_exact")
+        else:
+            cost.zero_(); qcost.zero_(); status.zero_()
+        ctx.scale = 1.0 / float(n) if normalise and n > 0 else 1.0
+        if normalise and n > 0:
+            cost.div_(float(n))                                    # (emd_approx's fp32 division)
+        ctx.save_for_backward(sample, ref)
+        ctx.assignment, ctx.inverse = assignment, inverse          # indices ride on ctx, as in NNDistanceFunction
+        ctx.mark_non_differentiable(assignment, qcost, status)
+        return cost, assignment, qcost, status
+
+    @staticmethod
+    def backward(ctx, grad_cost, _ga, _gq, _gs):
+        from .._lib import lib, check, current_stream
+        sample, ref = ctx.saved_tensors
+        need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        ga = torch.empty_like(sample) if need_a else None
+        gb = torch.empty_like(ref) if need_b else None
+        B, n = sample.shape[0], sample.shape[1]
+        if (need_a or need_b) and B > 0 and n > 0:
+            g = (grad_cost.float() * ctx.scale).contiguous()
+            with torch.cuda.device(sample.device):
+                check(lib().dpf_emd_exact_grad(B, n, sample.data_ptr(), ref.data_ptr(), ctx.assignment.data_ptr(), ctx.inverse.data_ptr(),
+                                               g.data_ptr(), ga.data_ptr() if need_a else None, gb.data_ptr() if need_b else None,
+                                               current_stream()), "emd_exact_grad")
+        return ga, gb, None, None, None, None
+
+
+def emd_exact_full(sample, ref, bits=20, max_rounds=EMD_EXACT_MAX_ROUNDS, form=0, normalise=False):
+    """(cost (B,) fp32 -- divided by n only with normalise --, assignment (B, n) int32, qcost (B,) int64, status (B,) int32) of dpf_emd_exact
+    (include/dpf_hip.h states the contract), with autograd through cost; no warning, no synchronisation.  form: 0 by size,
+    1 / 2 force the resident / streamed kernel (tests and tools)."""
+    _emd_exact_check(sample, "sample"); _emd_exact_check(ref, "ref")
+    if sample.shape[0] != ref.shape[0]:
+        raise RuntimeError("emd_exact needs as many clouds in both operands, got %d and %d" % (sample.shape[0], ref.shape[0]))
+    _emd_exact_sizes(sample.shape[1], ref.shape[1], bits, max_rounds)
+    return EMDExactFunction.apply(sample, ref, bits, max_rounds, form, normalise)
+
+
+def emd_exact(sample, ref, return_assignment=False, bits=20, max_rounds=EMD_EXACT_MAX_ROUNDS):
+    """(B,) exact EMD of equally sized clouds: the cost of the optimal one-to-one matching divided by n, emd_approx's normalisation.
+
+    The matching is the exact optimum on an integer grid of 2^bits steps over the pair's extent (include/dpf_hip.h):
+    its Euclidean cost is within 1.25 grid steps per point of the true optimum.  One autograd node; the backward treats the
+    matching as a constant and computes only the gradients that are asked for.  return_assignment: also the (B, n) int32
+    matching, point i of sample -> point assignment[i] of ref.
+    sample, ref: contiguous float32 CUDA (B, n, 3), anything else raises RuntimeError -- there is no CPU path.
+    max_rounds bounds the bidding rounds of a pair (default 2^20, about a hundred times what clouds of 2 048 points use).  A pair
+    that is refused (non-finite or overflowing coordinates) or reaches the cap gives NaN (assignment -1) and one RuntimeWarning
+    per call that names the status; looking at the statuses synchronises with the device."""
+    out, assignment, _, status = emd_exact_full(sample, ref, bits, max_rounds, normalise=True)
+    _emd_exact_warn(status, "emd_exact")
+    return (out, assignment) if return_assignment else out
+
+
+def pairwise_EMD_exact(clouds1, clouds2, bs=512, shard_rows=False, bits=20, max_rounds=EMD_EXACT_MAX_ROUNDS):
+    """(N1, N2) matrix of exact EMDs, out[i, j] = emd_exact(clouds1[i:i+1], clouds2[j:j+1]) bit for bit: pairwise_EMD's shape,
+    sharding and refusals with the exact matcher.  dpf_pairwise_emd_exact: one workgroup per pair, both sets read in place, no
+    assignment written.  `bs` bounds the pairs of a launch (whole rows, at least one); an entry's bits do not depend on it.  Unsolved pairs are NaN
+    and are named in one RuntimeWarning.  No autograd: inputs that would record a graph raise."""
+    from .._lib import lib, check, current_stream
+    if not (torch.is_tensor(clouds1) and torch.is_tensor(clouds2) and clouds1.is_cuda and clouds2.is_cuda):
+        raise RuntimeError("pairwise_EMD_exact needs CUDA tensors")
+    if clouds1.dtype != torch.float32 or clouds2.dtype != torch.float32:
+        raise RuntimeError("pairwise_EMD_exact needs float32 clouds")
+    if torch.is_grad_enabled() and (clouds1.requires_grad or clouds2.requires_grad):
+        raise RuntimeError("pairwise_EMD_exact has no backward: call it under torch.no_grad() or on tensors that do not require grad")
+    if clouds1.dim() != 3 or clouds2.dim() != 3 or clouds1.shape[2] != 3 or clouds2.shape[2] != 3:
+        raise RuntimeError("pairwise_EMD_exact needs point-major (N, n, 3) clouds, got %s and %s"
+                           % (tuple(clouds1.shape), tuple(clouds2.shape)))
+    clouds1, clouds2 = clouds1.contiguous(), clouds2.contiguous()
+    N1, n = clouds1.shape[0], clouds1.shape[1]
+    N2 = clouds2.shape[0]
+    _emd_exact_sizes(n, clouds2.shape[1], bits, max_rounds)
+    dev = clouds1.device
+    lo, hi = 0, N1
+    if shard_rows:
+        from .. import distributed as D
+        lo, hi = D.shard_bounds(N1)
+    emds = torch.empty((hi - lo, N2), dtype=torch.float32, device=dev)
+    if hi > lo and N2 > 0 and n > 0:
+        rows = max(1, min(hi - lo, max(1, int(bs)) // N2 if N2 <= bs else 1))
+        status = torch.empty((hi - lo, N2), dtype=torch.int32, device=dev)
+        qcost = torch.empty((rows, N2), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            ws, nbytes = _emd_exact_workspace(rows * N2, n, dev)
+            for r0 in range(lo, hi, rows):
+                nr = min(rows, hi - r0)
+                check(lib().dpf_pairwise_emd_exact(nr, N2, n, clouds1[r0].data_ptr(), clouds2.data_ptr(), int(bits), int(max_rounds), 0,
+                                                   qcost.data_ptr(), emds[r0 - lo].data_ptr(), status[r0 - lo].data_ptr(),
+                                                   ws.data_ptr(), nbytes, current_stream()), "pairwise_emd_exact")
+        emds.div_(float(n))                                     # (the fp32 division of emd_exact, in place)
+        _emd_exact_warn(status, "pairwise_EMD_exact")
+    if shard_rows:
+        from .. import distributed as D
+        emds = D.gather_clouds(emds)
+    return emds
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # The consumers of pairwise_CD in the reference's generative evaluation (evaluating.py:245-262): coverage, minimum matching
 # distance and the 1-NN two-sample accuracy over the (N1, N2) Chamfer matrices, the voxel-occupancy Jensen-Shannon divergence

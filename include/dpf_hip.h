@@ -852,6 +852,62 @@ int dpf_mesh_point_distance(int M, const float *vertices, const long *vertex_bou
 int dpf_mesh_point_distance_grad(int B, int N, long max_faces, const float *points, const int *point, const float *closest,
                                  const float *grad_dist, float *grad_points, dpf_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * Exact EMD (csrc/emd_exact.hip): the optimal one-to-one matching of two clouds a, b of n points each, (B, n, 3) fp32 point-major --
+ * a linear assignment problem on an integer cost grid, solved exactly by an epsilon-scaling auction in 64-bit integers.  Not a port:
+ * the reference has only the approximate matcher above.  tests/emd_exact_ref.py restates all of this in numpy.
+ *   The grid, per pair: lo / hi = the per-axis minimum / maximum over the 2n points (exact), E = the largest of the three
+ *     fl32(hi - lo).  E == 0: cost 0, qcost 0, the identity assignment, status 0.  Otherwise E = mant * 2^ex with mant in [0.5, 1)
+ *     (frexp) and s = 2^(bits - 1 - ex); the integer cost of the pair of points (i, j) is
+ *         c_ij = rint(sqrt((dx*dx + dy*dy) + dz*dz) * s),   d = a_i - b_j per axis,
+ *     every fp32 operation rounded on its own (no contraction), the square root correctly rounded, the product with s exact, rint
+ *     to nearest even; 0 <= c_ij < 2^bits.  bits in 1..24 (the Python default is 20).  Scaling both clouds by a power of two
+ *     changes no c_ij.
+ *   Refused pairs (status DPF_EMD_EXACT_REFUSED): any non-finite coordinate; E not finite; E * E not a normal fp32 number; 3 * (E * E)
+ *     not finite (a diagonal's square could overflow).
+ *   The auction minimises sum_i c_i,sigma(i) over permutations sigma.  Point i of a values object j (point j of b) at
+ *     u_ij = (n + 1) * c_ij + price_j, integer prices from 0.  A round: every unassigned i finds its lowest u (u1, at j1: the
+ *     LOWEST j among equal values) and second lowest (u2), all on the prices of the round's start, and bids price_j1 + (u2 - u1) +
+ *     epsilon for j1; every object that got bids takes the HIGHEST, among equal bids the LOWEST bidder, at that price, and its
+ *     previous owner is unassigned.  A phase runs rounds until every point is assigned.  epsilon is ((n + 1) << bits) >> 4 in the
+ *     first phase and falls by 3 bits per phase (never below 1); the phase at epsilon 1 is the last.  Prices are kept from phase to
+ *     phase, the assignment is reset.  With integer u and a final epsilon of 1 < (n + 1) / n the last assignment is an exact optimum
+ *     of the integer problem.  n == 1 is answered without a round.  Scaled costs stay below 2^38 and bids below 2^50 (a pair whose
+ *     bid reached 2^50 would end with DPF_EMD_EXACT_RANGE; no input is known to get there).
+ *   Outputs per pair: assignment (n) int32, optional (NULL: not written): point i of a is matched to point assignment[i] of b;
+ *     inverse (n) int32, optional: inverse[assignment[i]] = i; qcost int64 = sum_i c_i,assignment[i]; cost fp32 = the sum over
+ *     i = 0 .. n-1 ASCENDING, from 0, of the fp32 distances sqrt((dx*dx + dy*dy) + dz*dz) of the matched points (the arithmetic above);
+ *     status int32 >= 0: solved, the number of rounds used; < 0: one of the codes below, and then cost NaN, qcost -1, assignment and
+ *     inverse -1.  cost is NOT divided by n.
+ *   Bounded: max_rounds caps the rounds of a pair over all its phases; a pair that would need more ends with DPF_EMD_EXACT_CAP.
+ *     Every loop of the kernel runs over n, over the (at most 14) phases or over counted rounds: no input makes a launch spin.
+ *   Determinism: all outputs (status included) are bit-identical from run to run and depend on nothing but the pair's own 2n points,
+ *     bits and max_rounds -- not on the batch, the strides, the launch shape or the form.  One pair's refusal touches no other pair.
+ *   form: 0 = by size (dispatch.h: ee_form), 1 = resident: the second cloud in LDS, n <= 4096 (DPF_ENOSUP beyond), 2 = streamed: the
+ *     second cloud read from global memory and n words of bids per pair in workspace (dpf_emd_exact_workspace_bytes(pairs, n) bytes,
+ *     8-byte aligned; only the streamed form touches it).  n <= dpf_emd_exact_max_points() = 8192, DPF_ENOSUP beyond.
+ *   One workgroup per pair, one launch, the caller's stream, no synchronisation, no memset nodes; B = 0 or n = 0 launches nothing.
+ *   dpf_emd_exact: a_stride / b_stride = floats between consecutive clouds of an operand (3n for a dense batch; 0 broadcasts one cloud).
+ *   dpf_pairwise_emd_exact: the (N1, N2) matrix, pair (i, j) = clouds1[i] against clouds2[j], both sets dense and read in place;
+ *     qcost, cost, status are (N1, N2); no assignment is written.  N1 * N2 < 2^31.
+ *   dpf_emd_exact_grad: the assignment is a constant (as the reference's match_cost backward treats its matching):
+ *     grad_a[i] = grad_cost * ((a_i - b_j) / d) per axis with j = assignment[i] and d the fp32 distance above, 0 where d == 0;
+ *     grad_b[j] = the negative of that term at i = inverse[j].  Either output may be NULL (not computed); an index of -1 gives 0.
+ *     dense (B, n, 3) operands, grad_cost (B).  One launch, a gather, no atomics: bit-identical from run to run. */
+#define DPF_EMD_EXACT_REFUSED (-1)
+#define DPF_EMD_EXACT_CAP (-2)
+#define DPF_EMD_EXACT_RANGE (-3)
+int dpf_emd_exact_max_points(void);
+size_t dpf_emd_exact_workspace_bytes(long pairs, int n);
+int dpf_emd_exact(int B, int n, const float *a, long a_stride, const float *b, long b_stride, int bits, int max_rounds, int form,
+                  int *assignment, int *inverse, long long *qcost, float *cost, int *status, void *workspace,
+                  size_t workspace_bytes, dpf_stream_t stream);
+int dpf_pairwise_emd_exact(int N1, int N2, int n, const float *clouds1, const float *clouds2, int bits, int max_rounds, int form,
+                           long long *qcost, float *cost, int *status, void *workspace, size_t workspace_bytes,
+                           dpf_stream_t stream);
+int dpf_emd_exact_grad(int B, int n, const float *a, const float *b, const int *assignment, const int *inverse,
+                       const float *grad_cost, float *grad_a, float *grad_b, dpf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
