@@ -256,6 +256,25 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {     // maximum of
 #define DPF_T(i)
 #endif
 
+// r11: a wave's issue priority FALLS as it advances through a pass -- 3 in the first chunk's sweep, 2 in the second's, 1 from the
+// final threshold on (prune, scan, list, rounds, merge, epilogue); prologue and build run at the launch's 0.  The sixteen waves of
+// the workgroup are four per SIMD, launched a few hundred cycles apart, and between waves of equal priority the SIMD's arbiter
+// prefers the older one: the per-wave account (profiles/r11_nnm_phase_account_parent.txt) has the four waves of a SIMD finish
+// their own work 18 300 / 20 400 / 24 800 / 29 000 cycles after entry -- the oldest sweeps at almost its solo rate while the
+// youngest starves, then sweeps its second chunk and walks the whole latency chain of list, rounds and merge ALONE on its SIMD
+// (one wave per SIMD left from cycle 25 000 on, two from 21 000).  With the priority tied to progress the wave that is behind
+// wins the arbitration, the four stay within a chunk of each other and their latency chains overlap.  s_setprio orders issue
+// among waves and nothing else: no value, no address and no order of any sum depends on it.  (The 16-wave form only: the 8- and
+// 4-wave forms have two waves and one per SIMD, and keep the hardware's order.)
+template <int QW, int P>
+__device__ __forceinline__ void nnm_prio() {
+    if constexpr (QW == 16) {
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_setprio(P);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void glb_void;
 
@@ -465,6 +484,7 @@ __global__ __launch_bounds__(QW * 64) void nnm_kernel(MArgs args) {
             for (int c0 = 0; c0 < tn; c0 += SCH) {
                 const int cn = min(SCH, tn - c0);                             // wave-uniform
                 float mt[SCH];
+                if (c0 == 0) nnm_prio<QW, 3>(); else nnm_prio<QW, 2>();          // r11: the wave that is behind issues first (above); every pass anew
                 if (cn == SCH) {
                     const uint4 *fr = sfrag + c0 * 64 + lane;                 // tile u at fr[64 u]: immediate offsets
                     if constexpr (QW < 16) {
@@ -549,6 +569,7 @@ __global__ __launch_bounds__(QW * 64) void nnm_kernel(MArgs args) {
                 DPF_T(5 + 2 * (c0 / SCH))
                 if (c0 + SCH < tn) { dmask = smask; dcm = cm; }              // (wave-uniform) not the last chunk: it waits
             }
+            nnm_prio<QW, 1>();
             // thr is the pass's final threshold now.  The waiting chunk stays only where the lane's minimum of it reaches it.
 #ifdef DPF_PROFILE
             const unsigned dmask_all = dmask;
