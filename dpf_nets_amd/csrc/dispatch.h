@@ -71,6 +71,25 @@ inline Switches snapshot() {
 
 inline long ceil_div(long a, long b) { return (a + b - 1) / b; }
 
+// ---- launches cut to the grid's limits (mesh_sample.hip, point_mesh.hip, mesh_point.hip) -----------------------------------------
+constexpr long MAX_BLOCKS = 1L << 22;   // workgroups of one launch along x
+constexpr int MAX_SLOTS = 32768;        // batch slots of one launch (grid.y)
+// [0, total) in order, in pieces of at most `per`: launch(first, count) launches one and returns its error; the first non-zero
+// return ends the loop and is returned
+template <class Launch>
+inline int chunk_range(long total, long per, Launch &&launch) {
+    for (long i0 = 0; i0 < total; i0 += per)
+        if (const int e = launch(i0, total - i0 < per ? total - i0 : per)) return e;
+    return 0;
+}
+// the same over slots x blocks, the blocks of a piece of slots before the next slots: launch(b0, nb, k0, nk)
+template <class Launch>
+inline int chunk_grid(int slots, long blocks, Launch &&launch, int max_slots = MAX_SLOTS, long max_blocks = MAX_BLOCKS) {
+    return chunk_range(slots, max_slots, [&](long b0, long nb) {
+        return chunk_range(blocks, max_blocks, [&](long k0, long nk) { return launch((int)b0, (unsigned)nb, k0, (unsigned)nk); });
+    });
+}
+
 // ---- the eval flow stack (flow.hip, flow16.hip) ---------------------------------------------------------------------------
 enum class FlowKernel { Tile16Split, Tile16, Tile32 };
 // cw: compute waves of a 16-point workgroup (4 | 2); fw: waves of a 32-point workgroup (8 | 4 | 2 | 1); lpb: layers per LDS
@@ -268,45 +287,35 @@ inline TrainForm train_form(int ns, int nblk, int n_cu, const Switches &sw) {
     return f;
 }
 
-// ---- point-to-mesh distance (point_mesh.hip) --------------------------------------------------------------------------------
+// ---- point-to-mesh and mesh-to-cloud distance (point_mesh.hip, mesh_point.hip) --------------------------------------------------
 constexpr int PM_WG_POINTS = 256;   // query points of a workgroup: 4 waves, one point per lane
 constexpr int PM_TILE = 256;        // faces per LDS tile (16 KB of staged faces)
-constexpr int PM_FILL_WGS = 512;    // workgroups that fill the chip: two per CU (profiles/point_mesh_forms.txt)
-constexpr int PM_MAX_SPLITS = 1024;
-// Whole: every workgroup walks all tiles of its slot's mesh.  Split: the tiles are dealt round-robin to `splits` workgroups per
-// 256 points (64-bit atomic minimum, then a finishing launch) -- where the points alone leave CUs idle, as many splits as bring
-// the launch to PM_FILL_WGS workgroups, never more than the largest mesh has tiles.  force: 0 by size, 1 Whole, 2 Split (with
-// the splits the sizes ask for, at least one).  Total: any arguments give a form with 1 <= splits <= PM_MAX_SPLITS.
+constexpr int MP_WG_FACES = 256;    // mesh_point.hip: faces of a workgroup, 4 waves, one staged face per lane
+constexpr int MP_TILE = 256;        // points per LDS tile (4 KB)
+constexpr int PM_FILL_WGS = 512;    // workgroups that fill the chip: two per CU (profiles/point_mesh_forms.txt, mesh_point_forms.txt)
+constexpr int MAX_SPLITS = 1024, PM_MAX_SPLITS = MAX_SPLITS, MP_MAX_SPLITS = MAX_SPLITS;
+// A search keeps a workgroup's 256 row items (points; faces in mesh_point.hip) in registers and walks LDS tiles of the other side.
+// Whole: every workgroup walks all tiles of its slot.  Split: the tiles are dealt round-robin to `splits` workgroups per 256 row
+// items (64-bit atomic minimum, then a finishing launch) -- where the row items alone leave CUs idle, as many splits as bring the
+// launch to PM_FILL_WGS workgroups, never more than there are tiles.  force: 0 by size, 1 Whole, 2 Split (with the splits the
+// sizes ask for, at least one).  Total: any arguments >= 1 give a form with 1 <= splits <= MAX_SPLITS.
 enum class PMKernel { Whole, Split };
 struct PMForm { PMKernel kernel; int splits; };
-inline PMForm pm_form(int b, int n, long max_faces, int force) {
-    const long wgs = (b > 0 ? (long)b : 1) * (n > 0 ? ceil_div(n, PM_WG_POINTS) : 1);
-    const long tiles = max_faces > 0 ? ceil_div(max_faces, PM_TILE) : 1;
-    long splits = wgs >= PM_FILL_WGS ? 1 : ceil_div(PM_FILL_WGS, wgs);
+inline PMForm split_form(long workgroups, long tiles, int force) {
+    long splits = workgroups >= PM_FILL_WGS ? 1 : ceil_div(PM_FILL_WGS, workgroups);
     if (splits > tiles) splits = tiles;
-    if (splits > PM_MAX_SPLITS) splits = PM_MAX_SPLITS;
+    if (splits > MAX_SPLITS) splits = MAX_SPLITS;
     if (force == 1 || (force != 2 && splits < 2)) return {PMKernel::Whole, 1};
     return {PMKernel::Split, (int)splits};
 }
-
-// ---- mesh-to-cloud distance (mesh_point.hip) --------------------------------------------------------------------------------
-constexpr int MP_WG_FACES = 256;    // faces of a workgroup: 4 waves, one staged face per lane
-constexpr int MP_TILE = 256;        // points per LDS tile (4 KB)
-constexpr int MP_MAX_SPLITS = 1024;
-// The roles of pm_form's arguments swapped.  Whole: every workgroup walks all point tiles of its slot.  Split: the point tiles are
-// dealt round-robin to `splits` workgroups per 256 faces (64-bit atomic minimum, then a finishing launch) -- where
-// b * ceil(max_faces / 256) workgroups leave CUs idle, as many splits as bring the launch to PM_FILL_WGS workgroups, never more
-// than the clouds have point tiles.  force: 0 by size, 1 Whole, 2 Split (with the splits the sizes ask for, at least one).
-// Total: any arguments give a form with 1 <= splits <= MP_MAX_SPLITS.
+inline long at_least_one(long items, long per) { return items > 0 ? ceil_div(items, per) : 1; }
+// points in rows, tiles of the largest mesh's faces
+inline PMForm pm_form(int b, int n, long max_faces, int force) {
+    return split_form(at_least_one(b, 1) * at_least_one(n, PM_WG_POINTS), at_least_one(max_faces, PM_TILE), force);
+}
+// the roles swapped: the widest mesh's faces in rows, tiles of the cloud's points
 inline PMForm mp_form(int b, int n, long max_faces, int force) {
-    const long chunks = max_faces > 0 ? ceil_div(max_faces, MP_WG_FACES) : 1;
-    const long slots = b > 0 ? (long)b : 1;
-    const long tiles = n > 0 ? ceil_div(n, MP_TILE) : 1;
-    long splits = chunks >= PM_FILL_WGS || slots * chunks >= PM_FILL_WGS ? 1 : ceil_div(PM_FILL_WGS, slots * chunks);
-    if (splits > tiles) splits = tiles;
-    if (splits > MP_MAX_SPLITS) splits = MP_MAX_SPLITS;
-    if (force == 1 || (force != 2 && splits < 2)) return {PMKernel::Whole, 1};
-    return {PMKernel::Split, (int)splits};
+    return split_form(at_least_one(b, 1) * at_least_one(max_faces, MP_WG_FACES), at_least_one(n, MP_TILE), force);
 }
 
 // ---- exact EMD (emd_exact.hip) ------------------------------------------------------------------------------------------------

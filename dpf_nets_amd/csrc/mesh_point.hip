@@ -4,15 +4,15 @@
 // force, B * N * F point-triangle tests, the points broadcast from LDS.
 //
 // The contract is in include/dpf_hip.h.  The arithmetic of a pair is pm_stage / pm_eval of pm_pair.h, the one point_mesh.hip
-// uses: nothing here evaluates a pair in any other way.
+// uses: nothing here evaluates a pair in any other way; the host side of the two forms is its pm_search.  The store view, the slot
+// rule, the keys and the face area come from mesh_store.h.
 //   the minimum -- (distance bits << 32 | point) as an unsigned 64-bit key: non-negative fp32 bit patterns order as the floats
 //               do, the lowest point index wins among equal distances, and a minimum does not depend on the order it is taken in.
 //               A non-finite point is staged as the origin with a mask of all ones that is OR-ed into its distance bits: it can
 //               never be lower than the initial key, so it is never a face's nearest -- one integer operation per pair, no branch.
-//   the area  -- dpf_mesh_cdf_build's: e1 = p2 - p0, e2 = p2 - p1, the cross product as a product minus a product,
-//               sqrt((c0 * c0 + c1 * c1) + c2 * c2) / 2, nothing fused; 0 where it is not finite.
+//   the area  -- dpf_mesh_cdf_build's, by the one function both call (mesh_face_area); 0 where it is not finite.
 //
-// Two kernel forms (dispatch.h: mp_form).  Whole: a workgroup of 4 waves holds 256 faces of one slot, one staged face per lane in
+// Two kernel forms (dispatch.h: mp_form, a wrapper of split_form).  Whole: a workgroup of 4 waves holds 256 faces of one slot, one staged face per lane in
 // registers, and walks every 256-point tile of the slot's cloud.  Split: the tiles are dealt round-robin to `splits` workgroups
 // per 256 faces, each folds its minimum into a key buffer pre-set to all-ones with a 64-bit vector atomic minimum, and a
 // finishing launch unpacks the key.  Both forms write a column through mp_write, which evaluates the winning pair once more for
@@ -36,30 +36,25 @@ using namespace pm;
 
 constexpr int MP_THREADS = dispatch::MP_WG_FACES;   // threads = faces of a workgroup: one face per lane, 4 waves
 constexpr int MP_TILE = dispatch::MP_TILE;          // points per LDS tile: one point staged per thread
-constexpr int MP_MAX_SLOTS = 32768;                 // batch slots per launch (grid.y)
-constexpr long MP_MAX_BLOCKS = 1L << 22;            // face chunks per launch (grid.x)
 
 static_assert(MP_TILE == MP_THREADS, "one thread stages one point of a tile");
+static_assert(MP_THREADS == PM_THREADS, "pm_search launches workgroups of PM_THREADS");
 
 // the outputs of column f of slot b from its key; pts: the slot's points
-__device__ __forceinline__ void mp_write(const PMStore &st, const PMSlot &s, long f, unsigned long long key, const float *pts, size_t at,
+__device__ __forceinline__ void mp_write(const MeshStore &st, const MeshSlot &s, long f, unsigned long long key, const float *pts, size_t at,
                                          float *dist, int *point, float *closest, float *area) {
     const float nan = __builtin_nanf("");
     float d = nan, qx = nan, qy = nan, qz = nan, a = 0.0f;
     int k = -1;
+    // (the key is taken apart in place, not through mesh_store.h's helpers: with them mp_kernel<false> compiles to other code)
     if (s.ok && f < s.F && (unsigned int)key != 0xffffffffu) {              // (all ones: no finite point reached this face)
         k = (int)(unsigned int)key;
         const float px = pts[(size_t)k * 3], py = pts[(size_t)k * 3 + 1], pz = pts[(size_t)k * 3 + 2];
-        const unsigned int *fi = st.faces + (size_t)(s.fb + f) * 3;         // validated by dpf_mesh_cdf_build: flags[m] == 0
-        const float *p0 = st.vertices + (size_t)(s.vb + fi[0]) * 3, *p1 = st.vertices + (size_t)(s.vb + fi[1]) * 3,
-                    *p2 = st.vertices + (size_t)(s.vb + fi[2]) * 3;
-        const PMFace face = pm_stage(p0, p1, p2);
+        const MeshCorners c = mesh_corners(st, s.fb, s.vb, f);
+        const PMFace face = pm_stage(c.p0, c.p1, c.p2);
         pm_eval(face, px, py, pz, qx, qy, qz);
         d = __uint_as_float((unsigned int)(key >> 32));
-        const float ex = p2[0] - p0[0], ey = p2[1] - p0[1], ez = p2[2] - p0[2];
-        const float gx = p2[0] - p1[0], gy = p2[1] - p1[1], gz = p2[2] - p1[2];
-        const float c0 = ey * gz - ez * gy, c1 = ez * gx - ex * gz, c2 = ex * gy - ey * gx;
-        const float sa = sqrtf((c0 * c0 + c1 * c1) + c2 * c2) / 2.0f;
+        const float sa = mesh_face_area(c);
         a = sa <= 3.402823466e38f ? sa : 0.0f;                              // (false for NaN and for +inf)
     }
     dist[at] = d;
@@ -70,14 +65,14 @@ __device__ __forceinline__ void mp_write(const PMStore &st, const PMSlot &s, lon
 
 // point tiles t0, t0 + stride, ... of the slot's cloud; SPLIT: the minimum goes into keys, else straight to the outputs
 template <bool SPLIT>
-__global__ __launch_bounds__(MP_THREADS) void mp_kernel(PMStore st, int N, const float *__restrict__ points, const int *mesh_idx, long W,
+__global__ __launch_bounds__(MP_THREADS) void mp_kernel(MeshStore st, int N, const float *__restrict__ points, const int *mesh_idx, long W,
                                                         int b0, long blk0, unsigned long long *keys, float *dist, int *point,
                                                         float *closest, float *area) {
     __shared__ float4 pt[MP_TILE];                                          // x, y, z, the mask; a lane-uniform index broadcasts
     const int tid = threadIdx.x;
     const size_t b = (size_t)b0 + blockIdx.y;
     const long f0 = (blk0 + blockIdx.x) * MP_THREADS, f = f0 + tid;
-    const PMSlot s = pm_slot(st, mesh_idx, b);
+    const MeshSlot s = mesh_slot(st, mesh_idx, b);
     const float *pts = points + b * (size_t)N * 3;
     const bool mine = s.ok && f < s.F && f < W;
     PMFace face{};                                                          // (a lane without a face evaluates a point-like thin face; unused)
@@ -109,7 +104,7 @@ __global__ __launch_bounds__(MP_THREADS) void mp_kernel(PMStore st, int N, const
     }
     if (f >= W) return;
     const size_t at = b * (size_t)W + (size_t)f;
-    const unsigned long long key = ((unsigned long long)best << 32) | bestp;
+    const unsigned long long key = mesh_key(best, bestp);
     if (SPLIT) {
         if (mine && bestp != 0xffffffffu) atomicMin(&keys[at], key);
     } else {
@@ -117,19 +112,14 @@ __global__ __launch_bounds__(MP_THREADS) void mp_kernel(PMStore st, int N, const
     }
 }
 
-__global__ __launch_bounds__(MP_THREADS) void mp_fill_kernel(unsigned long long *keys, size_t i0, size_t n) {
-    const size_t i = i0 + (size_t)blockIdx.x * MP_THREADS + threadIdx.x;
-    if (i < n) keys[i] = ~0ull;
-}
-
-__global__ __launch_bounds__(MP_THREADS) void mp_finish_kernel(PMStore st, int N, const float *__restrict__ points, const int *mesh_idx,
+__global__ __launch_bounds__(MP_THREADS) void mp_finish_kernel(MeshStore st, int N, const float *__restrict__ points, const int *mesh_idx,
                                                                long W, int b0, long blk0, const unsigned long long *keys, float *dist,
                                                                int *point, float *closest, float *area) {
     const size_t b = (size_t)b0 + blockIdx.y;
     const long f = (blk0 + blockIdx.x) * MP_THREADS + threadIdx.x;
     if (f >= W) return;
     const size_t at = b * (size_t)W + (size_t)f;
-    const PMSlot s = pm_slot(st, mesh_idx, b);
+    const MeshSlot s = mesh_slot(st, mesh_idx, b);
     mp_write(st, s, f, keys[at], points + b * (size_t)N * 3, at, dist, point, closest, area);
 }
 
@@ -184,39 +174,17 @@ extern "C" int dpf_mesh_point_distance(int M, const float *vertices, const long 
     if (M < 1 || !vertices || !vertex_bounds || !faces || !face_bounds || !flags || (!points && N > 0) || !mesh_idx || !dist || !point)
         return DPF_EINVAL;
     const dispatch::PMForm mf = dispatch::mp_form(B, N, W, form);
-    const bool split = mf.kernel == dispatch::PMKernel::Split;
-    unsigned long long *keys = (unsigned long long *)workspace;
-    if (split && (!keys || ((uintptr_t)keys & 7) || workspace_bytes < dpf_mesh_point_workspace_bytes(B, W))) return DPF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e;
-    const PMStore st{M, vertices, vertex_bounds, faces, face_bounds, flags};
-    if (split) {
-        const size_t n = (size_t)B * (size_t)W, per = (size_t)MP_MAX_BLOCKS * MP_THREADS;
-        for (size_t i0 = 0; i0 < n; i0 += per) {
-            const size_t cnt = n - i0 < per ? n - i0 : per;
-            hipLaunchKernelGGL(mp_fill_kernel, dim3((unsigned)((cnt + MP_THREADS - 1) / MP_THREADS)), dim3(MP_THREADS), 0, s, keys, i0, n);
-            if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-        }
-    }
-    const long nblk = dispatch::ceil_div(W, MP_THREADS);
-    for (int pass = 0; pass < (split ? 2 : 1); ++pass)
-        for (int b0 = 0; b0 < B; b0 += MP_MAX_SLOTS) {
-            const unsigned nb = (unsigned)(B - b0 < MP_MAX_SLOTS ? B - b0 : MP_MAX_SLOTS);
-            for (long k0 = 0; k0 < nblk; k0 += MP_MAX_BLOCKS) {
-                const unsigned nk = (unsigned)(nblk - k0 < MP_MAX_BLOCKS ? nblk - k0 : MP_MAX_BLOCKS);
-                if (!split)
-                    hipLaunchKernelGGL(mp_kernel<false>, dim3(nk, nb), dim3(MP_THREADS), 0, s, st, N, points, mesh_idx, W, b0, k0, keys,
-                                       dist, point, closest, area);
-                else if (pass == 0)
-                    hipLaunchKernelGGL(mp_kernel<true>, dim3(nk, nb, (unsigned)mf.splits), dim3(MP_THREADS), 0, s, st, N, points, mesh_idx,
-                                       W, b0, k0, keys, dist, point, closest, area);
-                else
-                    hipLaunchKernelGGL(mp_finish_kernel, dim3(nk, nb), dim3(MP_THREADS), 0, s, st, N, points, mesh_idx, W, b0, k0, keys,
-                                       dist, point, closest, area);
-                if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-            }
-        }
-    return 0;
+    const MeshStore st{M, vertices, vertex_bounds, faces, face_bounds, flags};
+    unsigned long long *keys = (unsigned long long *)workspace;
+    auto pass = [=](auto kernel, int z) {
+        return [=](int b0, unsigned nb, long k0, unsigned nk) {
+            return mesh_launch(kernel, dim3(nk, nb, (unsigned)z), MP_THREADS, s, st, N, points, mesh_idx, W, b0, k0, keys, dist, point,
+                               closest, area);
+        };
+    };
+    return pm_search(mf, B, W, workspace, workspace_bytes, s, pass(mp_kernel<false>, 1), pass(mp_kernel<true>, mf.splits),
+                     pass(mp_finish_kernel, 1));
 }
 
 extern "C" int dpf_mesh_point_distance_grad(int B, int N, long max_faces, const float *points, const int *point, const float *closest,
@@ -224,16 +192,8 @@ extern "C" int dpf_mesh_point_distance_grad(int B, int N, long max_faces, const 
     if (B < 0 || N < 0 || max_faces < 0 || max_faces > 0x7fffffffL) return DPF_EINVAL;
     if (B == 0 || N == 0) return 0;
     if (!points || !grad_points || (max_faces > 0 && (!point || !closest || !grad_dist))) return DPF_EINVAL;
-    const long nblk = dispatch::ceil_div(N, MP_THREADS);
-    for (int b0 = 0; b0 < B; b0 += MP_MAX_SLOTS) {
-        const unsigned nb = (unsigned)(B - b0 < MP_MAX_SLOTS ? B - b0 : MP_MAX_SLOTS);
-        for (long k0 = 0; k0 < nblk; k0 += MP_MAX_BLOCKS) {
-            const unsigned nk = (unsigned)(nblk - k0 < MP_MAX_BLOCKS ? nblk - k0 : MP_MAX_BLOCKS);
-            hipLaunchKernelGGL(mp_grad_kernel, dim3(nk, nb), dim3(MP_THREADS), 0, (hipStream_t)stream, N, max_faces, b0, k0, points, point,
-                               closest, grad_dist, grad_points);
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return (int)e;
-        }
-    }
-    return 0;
+    return dispatch::chunk_grid(B, dispatch::ceil_div(N, MP_THREADS), [&](int b0, unsigned nb, long k0, unsigned nk) {
+        return mesh_launch(mp_grad_kernel, dim3(nk, nb), MP_THREADS, (hipStream_t)stream, N, max_faces, b0, k0, points, point, closest,
+                           grad_dist, grad_points);
+    });
 }

@@ -1,12 +1,10 @@
 // Surface sampling of triangle meshes into the collated training batch, on the device: what the reference's data loader does
 // on the host per item (lib/datasets/cloud_sampling.py:4-32 and the elementwise part of lib/datasets/cloud_transformations.py).
 //
-// The mesh store mirrors the layout of the reference's meshes.h5: packed fp32 vertices (sum V, 3), packed faces (sum F, 3) whose
-// vertex indices are LOCAL to their mesh, and two bounds arrays of M + 1 entries.
+// The mesh store's view, the slot rule, a face's corners and its area (numpy's fp32 sequence) are mesh_store.h's, shared with
+// point_mesh.hip and mesh_point.hip; the launches are cut to the grid's limits by dispatch.h's chunkers.
 //
-//   dpf_mesh_cdf_build -- once per store.  Per face the area as numpy forms it, in fp32, every operation rounded on its own:
-//       e1 = p2 - p0, e2 = p2 - p1, c = (e1.y*e2.z - e1.z*e2.y, e1.z*e2.x - e1.x*e2.z, e1.x*e2.y - e1.y*e2.x),
-//       area = sqrt((c0*c0 + c1*c1) + c2*c2) / 2.
+//   dpf_mesh_cdf_build -- once per store.  Per face the area (mesh_face_area).
 //     Per mesh the cumulative distribution over its faces in double.  The mesh is cut into tiles of MS_TILE faces counted from
 //     ITS OWN first face; a tile's areas are summed one after the other in face order (one thread: the order is the contract, and
 //     a running sum of non-negative terms is monotone, which a tree scan is not); the tile totals are summed one after the other
@@ -30,24 +28,16 @@
 #include <stdint.h>
 
 #include "dpf_hip.h"
+#include "dispatch.h"
+#include "mesh_store.h"
 #include "zero_fill.h"
 
 namespace {
 
 constexpr int MS_THREADS = 256;
 constexpr int MS_TILE = 256;                       // faces per scan tile == threads of a tile's workgroup
-constexpr long MS_MAX_BLOCKS = 1L << 22;           // workgroups per launch along x (the host loops chunk)
-constexpr int MS_MAX_SLOTS = 32768;                // batch slots per launch (grid.y)
 
 static_assert(MS_TILE == MS_THREADS, "one thread per face of a tile");
-
-struct MeshStoreArgs {
-    int M;
-    const float *vertices;
-    const long *vertex_bounds;
-    const unsigned int *faces;
-    const long *face_bounds;
-};
 
 // the m in [0, M) with bounds[m] <= x < bounds[m + 1] (bounds is increasing, bounds[0] <= x < bounds[M])
 __device__ __forceinline__ int ms_find(const long *bounds, int M, long x) {
@@ -68,7 +58,7 @@ __device__ __forceinline__ uint64_t ms_splitmix64(uint64_t x) {
 }
 
 // areas of one tile, their running sums in face order, the tile's total
-__global__ __launch_bounds__(MS_THREADS) void ms_tile_kernel(MeshStoreArgs a, const long *tile_bounds, long tile0, long ntiles,
+__global__ __launch_bounds__(MS_THREADS) void ms_tile_kernel(MeshStore a, const long *tile_bounds, long tile0, long ntiles,
                                                              double *cdf, double *tile_sum, unsigned int *flags) {
     __shared__ double run[MS_TILE];
     const long tile = tile0 + blockIdx.x;
@@ -86,12 +76,7 @@ __global__ __launch_bounds__(MS_THREADS) void ms_tile_kernel(MeshStoreArgs a, co
         if ((long)i0 >= V || (long)i1 >= V || (long)i2 >= V) {
             atomicOr(&flags[m], 1u);                                      // (no vertex is read through such an index)
         } else {
-            const float *p0 = a.vertices + (size_t)(vb + i0) * 3, *p1 = a.vertices + (size_t)(vb + i1) * 3,
-                        *p2 = a.vertices + (size_t)(vb + i2) * 3;
-            const float ax = p2[0] - p0[0], ay = p2[1] - p0[1], az = p2[2] - p0[2];
-            const float bx = p2[0] - p1[0], by = p2[1] - p1[1], bz = p2[2] - p1[2];
-            const float c0 = ay * bz - az * by, c1 = az * bx - ax * bz, c2 = ax * by - ay * bx;
-            const float s = sqrtf((c0 * c0 + c1 * c1) + c2 * c2) / 2.0f;
+            const float s = mesh_face_area(mesh_corners(a, fb, vb, f));
             if (s <= 3.402823466e38f) area = (double)s;                  // (false for NaN and for +inf)
             else atomicOr(&flags[m], 2u);
         }
@@ -125,7 +110,7 @@ __global__ __launch_bounds__(MS_THREADS) void ms_mesh_kernel(int M, const long *
     if (!(r > 0.0)) atomicOr(&flags[m], 4u);
 }
 
-__global__ __launch_bounds__(MS_THREADS) void ms_edge_kernel(MeshStoreArgs a, const long *tile_bounds, long tile0, long ntiles,
+__global__ __launch_bounds__(MS_THREADS) void ms_edge_kernel(MeshStore a, const long *tile_bounds, long tile0, long ntiles,
                                                              double *cdf, const double *tile_off, const double *total,
                                                              const unsigned int *flags) {
     const long tile = tile0 + blockIdx.x;
@@ -154,7 +139,6 @@ __global__ __launch_bounds__(MS_THREADS) void ms_variates_kernel(int S, size_t i
 
 struct MeshSampleArgs {
     const double *cdf;
-    const unsigned int *flags;
     const float *orig_c, *orig_s;
     int S, split, xform;
     const int *mesh_idx;
@@ -165,23 +149,21 @@ struct MeshSampleArgs {
     int *faces_out;
 };
 
-__global__ __launch_bounds__(MS_THREADS) void ms_sample_kernel(MeshStoreArgs st, MeshSampleArgs a, int b0) {
+__global__ __launch_bounds__(MS_THREADS) void ms_sample_kernel(MeshStore st, MeshSampleArgs a, int b0) {
     const int i = blockIdx.x * MS_THREADS + threadIdx.x;
     if (i >= a.S) return;
     const size_t b = (size_t)b0 + blockIdx.y, at = b * (size_t)a.S + i;
     const int N = a.split ? a.S >> 1 : a.S, j = a.split ? i >> 1 : i;
     float *out = ((a.split && (i & 1)) ? a.eval_cloud : a.cloud) + b * 3 * (size_t)N + j;
-    const int m = a.mesh_idx[b];
-    const bool known = m >= 0 && m < st.M;
-    const int F = known ? (int)(st.face_bounds[m + 1] - st.face_bounds[m]) : 0;
-    if (!known || F < 1 || a.flags[m] != 0u) {                            // never sampled: no face, no vertex of it is read
+    const MeshSlot sl = mesh_slot(st, a.mesh_idx, b);
+    if (!sl.ok) {                                                         // never sampled: no face, no vertex of it is read
         const float nan = __builtin_nanf("");
         out[0] = nan; out[N] = nan; out[2 * (size_t)N] = nan;
         if (a.faces_out) a.faces_out[at] = -1;
         return;
     }
-    const long fb = st.face_bounds[m], vb = st.vertex_bounds[m];
-    const double *edge = a.cdf + fb;
+    const int m = sl.m, F = sl.F;
+    const double *edge = a.cdf + sl.fb;
     const double uu = a.u[at];
     int lo = 0, hi = F;                                                   // the first k with edge[k] > u
     while (lo < hi) {
@@ -189,9 +171,8 @@ __global__ __launch_bounds__(MS_THREADS) void ms_sample_kernel(MeshStoreArgs st,
         if (edge[mid] > uu) hi = mid; else lo = mid + 1;
     }
     const int k = lo < F ? lo : F - 1;                                    // (only a u outside [0, 1) gets here past the end)
-    const unsigned int *fi = st.faces + (size_t)(fb + k) * 3;             // validated by dpf_mesh_cdf_build: flags[m] == 0
-    const float *p0 = st.vertices + (size_t)(vb + fi[0]) * 3, *p1 = st.vertices + (size_t)(vb + fi[1]) * 3,
-                *p2 = st.vertices + (size_t)(vb + fi[2]) * 3;
+    const MeshCorners cr = mesh_corners(st, sl.fb, sl.vb, k);
+    const float *p0 = cr.p0, *p1 = cr.p1, *p2 = cr.p2;
     float t1 = a.s1[at], t2 = a.s2[at];
     if (t1 + t2 > 1.0f) { t1 = 1.0f - t1; t2 = 1.0f - t2; }
     const float os = (a.xform & 1) ? a.orig_s[m] : 1.0f;
@@ -225,25 +206,19 @@ extern "C" int dpf_mesh_cdf_build(int M, const float *vertices, const long *vert
         return DPF_EINVAL;
     if (workspace_bytes < dpf_mesh_cdf_workspace_bytes(M, n_tiles) || ((uintptr_t)workspace & 7) || ((uintptr_t)cdf & 7)) return DPF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = dpf_zero_async(flags, (size_t)M * 4, st);
-    if (e != hipSuccess) return (int)e;
+    int e = (int)dpf_zero_async(flags, (size_t)M * 4, st);
+    if (e) return e;
     double *tile_sum = (double *)workspace, *total = tile_sum + n_tiles;
-    const MeshStoreArgs a{M, vertices, vertex_bounds, faces, face_bounds};
-    for (long t0 = 0; t0 < n_tiles; t0 += MS_MAX_BLOCKS) {
-        const long nb = n_tiles - t0 < MS_MAX_BLOCKS ? n_tiles - t0 : MS_MAX_BLOCKS;
-        hipLaunchKernelGGL(ms_tile_kernel, dim3((unsigned)nb), dim3(MS_THREADS), 0, st, a, tile_bounds, t0, n_tiles, cdf, tile_sum, flags);
-        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(ms_mesh_kernel, dim3((unsigned)((M + MS_THREADS - 1) / MS_THREADS)), dim3(MS_THREADS), 0, st, M, tile_bounds,
-                       tile_sum, total, flags);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    for (long t0 = 0; t0 < n_tiles; t0 += MS_MAX_BLOCKS) {
-        const long nb = n_tiles - t0 < MS_MAX_BLOCKS ? n_tiles - t0 : MS_MAX_BLOCKS;
-        hipLaunchKernelGGL(ms_edge_kernel, dim3((unsigned)nb), dim3(MS_THREADS), 0, st, a, tile_bounds, t0, n_tiles, cdf, tile_sum, total,
-                           flags);
-        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    }
-    return 0;
+    const MeshStore a{M, vertices, vertex_bounds, faces, face_bounds, flags};
+    e = dispatch::chunk_range(n_tiles, dispatch::MAX_BLOCKS, [&](long t0, long nb) {
+        return mesh_launch(ms_tile_kernel, dim3((unsigned)nb), MS_THREADS, st, a, tile_bounds, t0, n_tiles, cdf, tile_sum, flags);
+    });
+    if (e) return e;
+    e = mesh_launch(ms_mesh_kernel, dim3((unsigned)((M + MS_THREADS - 1) / MS_THREADS)), MS_THREADS, st, M, tile_bounds, tile_sum, total, flags);
+    if (e) return e;
+    return dispatch::chunk_range(n_tiles, dispatch::MAX_BLOCKS, [&](long t0, long nb) {
+        return mesh_launch(ms_edge_kernel, dim3((unsigned)nb), MS_THREADS, st, a, tile_bounds, t0, n_tiles, cdf, tile_sum, total, flags);
+    });
 }
 
 extern "C" int dpf_mesh_variates(int B, int S, unsigned long long seed, unsigned long long step, double *u, float *s1, float *s2,
@@ -259,15 +234,11 @@ extern "C" int dpf_mesh_variates(int B, int S, unsigned long long seed, unsigned
     base = (base ^ (base >> 30)) * 0xBF58476D1CE4E5B9ull;
     base = (base ^ (base >> 27)) * 0x94D049BB133111EBull;
     base ^= base >> 31;
-    const size_t n = (size_t)B * (size_t)S, per = (size_t)MS_MAX_BLOCKS * MS_THREADS;
-    for (size_t i0 = 0; i0 < n; i0 += per) {
-        const size_t cnt = n - i0 < per ? n - i0 : per;
-        hipLaunchKernelGGL(ms_variates_kernel, dim3((unsigned)((cnt + MS_THREADS - 1) / MS_THREADS)), dim3(MS_THREADS), 0,
-                           (hipStream_t)stream, S, i0, n, base, u, s1, s2);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    }
-    return 0;
+    const size_t n = (size_t)B * (size_t)S;
+    return dispatch::chunk_range((long)n, dispatch::MAX_BLOCKS * MS_THREADS, [&](long i0, long cnt) {
+        return mesh_launch(ms_variates_kernel, dim3((unsigned)dispatch::ceil_div(cnt, MS_THREADS)), MS_THREADS, (hipStream_t)stream, S, i0, n,
+                           base, u, s1, s2);
+    });
 }
 
 extern "C" int dpf_mesh_sample(int M, const float *vertices, const long *vertex_bounds, const unsigned int *faces,
@@ -280,16 +251,12 @@ extern "C" int dpf_mesh_sample(int M, const float *vertices, const long *vertex_
     if (split != 0 && split != 1) return DPF_EINVAL;
     if (split && ((S & 1) || !eval_cloud)) return DPF_EINVAL;
     if ((xform & ~15) || ((xform & 1) && !orig_s) || ((xform & 2) && !orig_c)) return DPF_EINVAL;
-    if ((long)((S + MS_THREADS - 1) / MS_THREADS) > MS_MAX_BLOCKS) return DPF_ENOSUP;
-    const MeshStoreArgs st{M, vertices, vertex_bounds, faces, face_bounds};
-    const MeshSampleArgs a{cdf, flags, orig_c, orig_s, S, split, xform, mesh_idx, u, s1, s2, {shift_x, shift_y, shift_z}, scale,
+    if ((long)((S + MS_THREADS - 1) / MS_THREADS) > dispatch::MAX_BLOCKS) return DPF_ENOSUP;
+    const MeshStore st{M, vertices, vertex_bounds, faces, face_bounds, flags};
+    const MeshSampleArgs a{cdf, orig_c, orig_s, S, split, xform, mesh_idx, u, s1, s2, {shift_x, shift_y, shift_z}, scale,
                            cloud, eval_cloud, faces_out};
-    for (int b0 = 0; b0 < B; b0 += MS_MAX_SLOTS) {
-        const int nb = B - b0 < MS_MAX_SLOTS ? B - b0 : MS_MAX_SLOTS;
-        hipLaunchKernelGGL(ms_sample_kernel, dim3((unsigned)((S + MS_THREADS - 1) / MS_THREADS), (unsigned)nb), dim3(MS_THREADS), 0,
-                           (hipStream_t)stream, st, a, b0);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    }
-    return 0;
+    return dispatch::chunk_range(B, dispatch::MAX_SLOTS, [&](long b0, long nb) {
+        return mesh_launch(ms_sample_kernel, dim3((unsigned)((S + MS_THREADS - 1) / MS_THREADS), (unsigned)nb), MS_THREADS, (hipStream_t)stream,
+                           st, a, (int)b0);
+    });
 }

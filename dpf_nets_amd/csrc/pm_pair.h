@@ -11,6 +11,9 @@
 //               costs no division.  A thin face is the nearest of its three edges (segments, or points where an edge has no
 //               length), ties to AB, then AC, then BC.  The closest point is q = a + v * ab + w * ac, the distance |p - q|^2.
 //
+// The store view, the slot rule, a face's corners and the keys of the minimum come from mesh_store.h.  Below the arithmetic, what
+// the host side of both searches shares: pm_fill_kernel and pm_search, the driver of the Whole and the Split form.
+//
 // Both translation units are compiled with -ffp-contract=off: the fused operations are the fmaf calls written out below and no
 // others.  fp32 division (staging only) is the correctly rounded one.
 #ifndef DPF_PM_PAIR_H
@@ -18,18 +21,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dpf_hip.h"
+#include "dispatch.h"
+#include "mesh_store.h"
+
 namespace pm {
 
 constexpr float PM_THIN = 6.103515625e-05f;         // 2^-14
-
-struct PMStore {
-    int M;
-    const float *vertices;
-    const long *vertex_bounds;
-    const unsigned int *faces;
-    const long *face_bounds;
-    const unsigned int *flags;
-};
 
 // what the lanes of a wave share about a face (point_mesh.hip), or what a lane keeps of its own face (mesh_point.hip)
 struct PMFace {
@@ -106,26 +104,41 @@ __device__ __forceinline__ float pm_eval(const PMFace &f, float px, float py, fl
     return pm_point(f, px, py, pz, v, w, qx, qy, qz);
 }
 
-struct PMSlot { bool ok; long fb, vb; int F; };
-
-__device__ __forceinline__ PMSlot pm_slot(const PMStore &st, const int *mesh_idx, size_t b) {
-    PMSlot s{false, 0, 0, 0};
-    const int m = mesh_idx[b];
-    if (m < 0 || m >= st.M || st.flags[m] != 0u) return s;                  // nothing of such a mesh is read
-    s.fb = st.face_bounds[m]; s.vb = st.vertex_bounds[m];
-    s.F = (int)(st.face_bounds[m + 1] - s.fb);
-    s.ok = s.F >= 1;
-    return s;
-}
-
-__device__ __forceinline__ PMFace pm_stage_face(const PMStore &st, const PMSlot &s, int face) {
-    const unsigned int *fi = st.faces + (size_t)(s.fb + face) * 3;          // validated by dpf_mesh_cdf_build: flags[m] == 0
-    return pm_stage(st.vertices + (size_t)(s.vb + fi[0]) * 3, st.vertices + (size_t)(s.vb + fi[1]) * 3,
-                    st.vertices + (size_t)(s.vb + fi[2]) * 3);
+__device__ __forceinline__ PMFace pm_stage_face(const MeshStore &st, const MeshSlot &s, int face) {
+    const MeshCorners c = mesh_corners(st, s.fb, s.vb, face);
+    return pm_stage(c.p0, c.p1, c.p2);
 }
 
 __device__ __forceinline__ bool pm_finite(float x, float y, float z) {
     return fabsf(x) <= 3.402823466e38f && fabsf(y) <= 3.402823466e38f && fabsf(z) <= 3.402823466e38f;   // (false for NaN)
+}
+
+// ---- the host side of a search in either direction ------------------------------------------------------------------------------
+constexpr int PM_THREADS = dispatch::PM_WG_POINTS;  // threads of every workgroup of both directions: 4 waves, one row item per lane
+static_assert(PM_THREADS == dispatch::MP_WG_FACES, "both directions launch the same workgroups");
+
+static __global__ __launch_bounds__(PM_THREADS) void pm_fill_kernel(unsigned long long *keys, size_t i0, size_t n) {
+    const size_t i = i0 + (size_t)blockIdx.x * PM_THREADS + threadIdx.x;
+    if (i < n) keys[i] = ~0ull;
+}
+
+// B slots of `row` items (points, or columns of faces), PM_THREADS items per workgroup.  whole / split / finish launch one chunk
+// (b0, nb, k0, nk) of the grid and return the launch's error.  Whole: one pass.  Split: the keys (the workspace, B * row of them)
+// are set to all ones, `split` folds its minima into them, `finish` unpacks them.
+template <class Whole, class Split, class Finish>
+inline int pm_search(dispatch::PMForm form, int B, long row, void *workspace, size_t workspace_bytes, hipStream_t stream, Whole whole,
+                     Split split, Finish finish) {
+    const long blocks = dispatch::ceil_div(row, PM_THREADS);
+    if (form.kernel == dispatch::PMKernel::Whole) return dispatch::chunk_grid(B, blocks, whole);
+    unsigned long long *keys = (unsigned long long *)workspace;
+    const size_t n = (size_t)B * (size_t)row;
+    if (!keys || ((uintptr_t)keys & 7) || workspace_bytes < n * sizeof(*keys)) return DPF_EINVAL;
+    int e = dispatch::chunk_range((long)n, dispatch::MAX_BLOCKS * PM_THREADS, [&](long i0, long cnt) {
+        return mesh_launch(pm_fill_kernel, dim3((unsigned)dispatch::ceil_div(cnt, PM_THREADS)), PM_THREADS, stream, keys, i0, n);
+    });
+    if (!e) e = dispatch::chunk_grid(B, blocks, split);
+    if (!e) e = dispatch::chunk_grid(B, blocks, finish);
+    return e;
 }
 
 }  // namespace pm

@@ -2,7 +2,8 @@
 // point the minimum over the faces of its slot's mesh of the squared distance to the closed triangle, a face that attains it
 // and the closest point on that face.  Brute force, B * N * F point-triangle tests, the faces broadcast from LDS.
 //
-// The contract is in include/dpf_hip.h; the arithmetic of a pair lives in pm_pair.h, shared with mesh_point.hip.  In short
+// The contract is in include/dpf_hip.h; the arithmetic of a pair and the host side of the two forms live in pm_pair.h, shared with
+// mesh_point.hip; the store view, the slot rule and the keys in mesh_store.h, shared with mesh_sample.hip too.  In short
 //   pm_stage -- per face, once per tile and workgroup: 16 floats every lane of a wave shares (corner a, the edge vectors
 //               ab = b - a and ac = c - a, their dot products aa, g = ab.ac, cc, and the reciprocals 1/aa, 1/cc, 1/|c - b|^2,
 //               1/det with det = aa * cc - g * g).  A face is THIN when !(det > 2^-14 * (aa * cc)): degenerate faces (zero area,
@@ -15,7 +16,7 @@
 //   the minimum -- (distance bits << 32 | face) as an unsigned 64-bit key: non-negative fp32 bit patterns order as the floats
 //               do, the lowest face index wins among equal distances, and a minimum does not depend on the order it is taken in.
 //
-// Two kernel forms (dispatch.h: pm_form).  Whole: a workgroup of 4 waves holds 256 points of one slot, one per lane, and walks
+// Two kernel forms (dispatch.h: pm_form, a wrapper of split_form), driven by pm_pair.h's pm_search.  Whole: a workgroup of 4 waves holds 256 points of one slot, one per lane, and walks
 // every tile of the slot's mesh.  Split: the tiles of a mesh are dealt round-robin to `splits` workgroups per 256 points, each
 // folds its minimum into a key buffer pre-set to all-ones with a 64-bit vector atomic minimum, and a finishing launch unpacks
 // the key and recomputes the closest point on the winning face with the same pm_stage / pm_eval.
@@ -31,26 +32,23 @@
 
 namespace {
 
-using namespace pm;                                 // PMStore, PMFace, pm_stage, pm_eval, pm_slot, ...: the pair arithmetic (pm_pair.h)
+using namespace pm;                                 // PMFace, pm_stage, pm_eval, PM_THREADS (= points of a workgroup), pm_search, ...
 
-constexpr int PM_THREADS = dispatch::PM_WG_POINTS;  // threads = points of a workgroup: one point per lane, 4 waves
 constexpr int PM_TILE = dispatch::PM_TILE;          // faces per LDS tile: one face staged per thread
-constexpr int PM_MAX_SLOTS = 32768;                 // batch slots per launch (grid.y)
-constexpr long PM_MAX_BLOCKS = 1L << 22;            // point chunks per launch (grid.x)
 
 static_assert(PM_TILE == PM_THREADS, "one thread stages one face of a tile");
 
 // the outputs of one point from its key
-__device__ __forceinline__ void pm_write(const PMStore &st, const PMSlot &s, bool finite, unsigned long long key, float px, float py,
+__device__ __forceinline__ void pm_write(const MeshStore &st, const MeshSlot &s, bool finite, unsigned long long key, float px, float py,
                                          float pz, size_t at, float *dist, int *face, float *closest) {
     const float nan = __builtin_nanf("");
     float d = nan, qx = nan, qy = nan, qz = nan;
     int k = -1;
     if (s.ok && finite) {
-        k = (int)(unsigned int)key;
+        k = mesh_key_index(key);
         const PMFace f = pm_stage_face(st, s, k);
         pm_eval(f, px, py, pz, qx, qy, qz);
-        d = __uint_as_float((unsigned int)(key >> 32));
+        d = mesh_key_dist(key);
     }
     dist[at] = d;
     face[at] = k;
@@ -59,7 +57,7 @@ __device__ __forceinline__ void pm_write(const PMStore &st, const PMSlot &s, boo
 
 // tiles t0, t0 + stride, ... of the slot's mesh; SPLIT: the minimum goes into keys, else straight to the outputs
 template <bool SPLIT>
-__global__ __launch_bounds__(PM_THREADS) void pm_kernel(PMStore st, int N, const float *__restrict__ points, const int *mesh_idx,
+__global__ __launch_bounds__(PM_THREADS) void pm_kernel(MeshStore st, int N, const float *__restrict__ points, const int *mesh_idx,
                                                         int b0, long blk0, unsigned long long *keys, float *dist, int *face,
                                                         float *closest) {
     __shared__ float4 q0[PM_TILE], q1[PM_TILE], q2[PM_TILE], q3[PM_TILE];   // structure of arrays: a lane-uniform index broadcasts
@@ -67,7 +65,7 @@ __global__ __launch_bounds__(PM_THREADS) void pm_kernel(PMStore st, int N, const
     const size_t b = (size_t)b0 + blockIdx.y;
     const long n = (blk0 + blockIdx.x) * PM_THREADS + tid;
     const size_t at = b * (size_t)N + (size_t)n;
-    const PMSlot s = pm_slot(st, mesh_idx, b);
+    const MeshSlot s = mesh_slot(st, mesh_idx, b);
     float px = 0.0f, py = 0.0f, pz = 0.0f;
     bool finite = false;
     if (n < N) {
@@ -103,7 +101,7 @@ __global__ __launch_bounds__(PM_THREADS) void pm_kernel(PMStore st, int N, const
         }
     }
     if (n >= N) return;
-    const unsigned long long key = ((unsigned long long)best << 32) | bestf;
+    const unsigned long long key = mesh_key(best, bestf);
     if (SPLIT) {
         if (s.ok && finite && bestf != 0xffffffffu) atomicMin(&keys[at], key);
     } else {
@@ -111,19 +109,14 @@ __global__ __launch_bounds__(PM_THREADS) void pm_kernel(PMStore st, int N, const
     }
 }
 
-__global__ __launch_bounds__(PM_THREADS) void pm_fill_kernel(unsigned long long *keys, size_t i0, size_t n) {
-    const size_t i = i0 + (size_t)blockIdx.x * PM_THREADS + threadIdx.x;
-    if (i < n) keys[i] = ~0ull;
-}
-
-__global__ __launch_bounds__(PM_THREADS) void pm_finish_kernel(PMStore st, int N, const float *__restrict__ points, const int *mesh_idx,
+__global__ __launch_bounds__(PM_THREADS) void pm_finish_kernel(MeshStore st, int N, const float *__restrict__ points, const int *mesh_idx,
                                                                int b0, long blk0, const unsigned long long *keys, float *dist, int *face,
                                                                float *closest) {
     const size_t b = (size_t)b0 + blockIdx.y;
     const long n = (blk0 + blockIdx.x) * PM_THREADS + threadIdx.x;
     if (n >= N) return;
     const size_t at = b * (size_t)N + (size_t)n;
-    const PMSlot s = pm_slot(st, mesh_idx, b);
+    const MeshSlot s = mesh_slot(st, mesh_idx, b);
     const float px = points[at * 3], py = points[at * 3 + 1], pz = points[at * 3 + 2];
     pm_write(st, s, pm_finite(px, py, pz), keys[at], px, py, pz, at, dist, face, closest);
 }
@@ -160,39 +153,16 @@ extern "C" int dpf_point_mesh_distance(int M, const float *vertices, const long 
         return DPF_EINVAL;
     if (max_faces < 1) return DPF_EINVAL;
     const dispatch::PMForm pf = dispatch::pm_form(B, N, max_faces, form);
-    const bool split = pf.kernel == dispatch::PMKernel::Split;
-    unsigned long long *keys = (unsigned long long *)workspace;
-    if (split && (!keys || ((uintptr_t)keys & 7) || workspace_bytes < dpf_point_mesh_workspace_bytes(B, N))) return DPF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e;
-    const PMStore st{M, vertices, vertex_bounds, faces, face_bounds, flags};
-    if (split) {
-        const size_t n = (size_t)B * (size_t)N, per = (size_t)PM_MAX_BLOCKS * PM_THREADS;
-        for (size_t i0 = 0; i0 < n; i0 += per) {
-            const size_t cnt = n - i0 < per ? n - i0 : per;
-            hipLaunchKernelGGL(pm_fill_kernel, dim3((unsigned)((cnt + PM_THREADS - 1) / PM_THREADS)), dim3(PM_THREADS), 0, s, keys, i0, n);
-            if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-        }
-    }
-    const long nblk = dispatch::ceil_div(N, PM_THREADS);
-    for (int pass = 0; pass < (split ? 2 : 1); ++pass)
-        for (int b0 = 0; b0 < B; b0 += PM_MAX_SLOTS) {
-            const unsigned nb = (unsigned)(B - b0 < PM_MAX_SLOTS ? B - b0 : PM_MAX_SLOTS);
-            for (long k0 = 0; k0 < nblk; k0 += PM_MAX_BLOCKS) {
-                const unsigned nk = (unsigned)(nblk - k0 < PM_MAX_BLOCKS ? nblk - k0 : PM_MAX_BLOCKS);
-                if (!split)
-                    hipLaunchKernelGGL(pm_kernel<false>, dim3(nk, nb), dim3(PM_THREADS), 0, s, st, N, points, mesh_idx, b0, k0, keys, dist,
-                                       face, closest);
-                else if (pass == 0)
-                    hipLaunchKernelGGL(pm_kernel<true>, dim3(nk, nb, (unsigned)pf.splits), dim3(PM_THREADS), 0, s, st, N, points, mesh_idx,
-                                       b0, k0, keys, dist, face, closest);
-                else
-                    hipLaunchKernelGGL(pm_finish_kernel, dim3(nk, nb), dim3(PM_THREADS), 0, s, st, N, points, mesh_idx, b0, k0, keys, dist,
-                                       face, closest);
-                if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-            }
-        }
-    return 0;
+    const MeshStore st{M, vertices, vertex_bounds, faces, face_bounds, flags};
+    unsigned long long *keys = (unsigned long long *)workspace;
+    auto pass = [=](auto kernel, int z) {
+        return [=](int b0, unsigned nb, long k0, unsigned nk) {
+            return mesh_launch(kernel, dim3(nk, nb, (unsigned)z), PM_THREADS, s, st, N, points, mesh_idx, b0, k0, keys, dist, face, closest);
+        };
+    };
+    return pm_search(pf, B, N, workspace, workspace_bytes, s, pass(pm_kernel<false>, 1), pass(pm_kernel<true>, pf.splits),
+                     pass(pm_finish_kernel, 1));
 }
 
 extern "C" int dpf_point_mesh_distance_grad(int B, int N, const float *points, const float *closest, const float *grad_dist,
@@ -200,13 +170,9 @@ extern "C" int dpf_point_mesh_distance_grad(int B, int N, const float *points, c
     if (B < 0 || N < 0) return DPF_EINVAL;
     if (B == 0 || N == 0) return 0;
     if (!points || !closest || !grad_dist || !grad_points) return DPF_EINVAL;
-    const size_t n = (size_t)B * (size_t)N, per = (size_t)PM_MAX_BLOCKS * PM_THREADS;
-    for (size_t i0 = 0; i0 < n; i0 += per) {
-        const size_t cnt = n - i0 < per ? n - i0 : per;
-        hipLaunchKernelGGL(pm_grad_kernel, dim3((unsigned)((cnt + PM_THREADS - 1) / PM_THREADS)), dim3(PM_THREADS), 0, (hipStream_t)stream,
-                           i0, n, points, closest, grad_dist, grad_points);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    }
-    return 0;
+    const size_t n = (size_t)B * (size_t)N;
+    return dispatch::chunk_range((long)n, dispatch::MAX_BLOCKS * PM_THREADS, [&](long i0, long cnt) {
+        return mesh_launch(pm_grad_kernel, dim3((unsigned)dispatch::ceil_div(cnt, PM_THREADS)), PM_THREADS, (hipStream_t)stream, i0, n,
+                           points, closest, grad_dist, grad_points);
+    });
 }

@@ -108,8 +108,7 @@ class MeshStore(object):
         nbytes = lib().dpf_mesh_cdf_workspace_bytes(M, n_tiles)
         ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
-            check(lib().dpf_mesh_cdf_build(M, self.vertices.data_ptr(), self.vertex_bounds.data_ptr(), self.faces.data_ptr(),
-                                           self.face_bounds.data_ptr(), self.tile_bounds.data_ptr(), n_tiles, self.cdf.data_ptr(),
+            check(lib().dpf_mesh_cdf_build(*self.abi_args()[:5], self.tile_bounds.data_ptr(), n_tiles, self.cdf.data_ptr(),
                                            self.flags.data_ptr(), ws.data_ptr(), nbytes, current_stream()), "mesh_cdf_build")
             flags = self.flags.cpu().numpy()                                                          # the one synchronisation
         self.bad = {int(m): int(flags[m]) for m in np.flatnonzero(flags)}
@@ -128,6 +127,12 @@ class MeshStore(object):
 
     def __len__(self):
         return self.num_meshes
+
+    def abi_args(self):
+        """The store as the C ABI takes it: (M, vertices, vertex_bounds, faces, face_bounds, flags).  The entries that take no
+        flags here (dpf_mesh_cdf_build, dpf_mesh_sample) pass the leading five."""
+        return (self.num_meshes, self.vertices.data_ptr(), self.vertex_bounds.data_ptr(), self.faces.data_ptr(),
+                self.face_bounds.data_ptr(), self.flags.data_ptr())
 
 
 class CloudTransform(object):
@@ -250,8 +255,7 @@ def sample_clouds(store, mesh_indices, cloud_size, return_eval_cloud=False, seed
             out["eval_cloud"] = torch.empty((B, 3, N), dtype=torch.float32, device=dev)
         faces = torch.empty((B, S), dtype=torch.int32, device=dev) if return_faces else None
         ptr = lambda t: None if t is None else t.data_ptr()                                           # noqa: E731
-        check(L.dpf_mesh_sample(store.num_meshes, store.vertices.data_ptr(), store.vertex_bounds.data_ptr(), store.faces.data_ptr(),
-                                store.face_bounds.data_ptr(), store.cdf.data_ptr(), store.flags.data_ptr(), ptr(store.orig_c),
+        check(L.dpf_mesh_sample(*store.abi_args()[:5], store.cdf.data_ptr(), store.flags.data_ptr(), ptr(store.orig_c),
                                 ptr(store.orig_s), B, S, slots.data_ptr(), u.data_ptr(), s1.data_ptr(), s2.data_ptr(), int(split), mask,
                                 float(shift[0]), float(shift[1]), float(shift[2]), float(scale), out["cloud"].data_ptr(),
                                 ptr(out.get("eval_cloud")), ptr(faces), current_stream()), "mesh_sample")

@@ -22,11 +22,6 @@ from ..datasets.sampling import MeshStore, CloudTransform
 __all__ = ["point_mesh_distance", "surface_accuracy", "mesh_point_distance", "surface_completeness", "surface_chamfer"]
 
 
-def _store_args(store):
-    return (store.num_meshes, store.vertices.data_ptr(), store.vertex_bounds.data_ptr(), store.faces.data_ptr(),
-            store.face_bounds.data_ptr(), store.flags.data_ptr())
-
-
 def _launch(points, store, slots, max_faces, form, want_closest):
     B, N = int(points.shape[0]), int(points.shape[1])
     dev = points.device
@@ -38,7 +33,7 @@ def _launch(points, store, slots, max_faces, form, want_closest):
         with torch.cuda.device(dev):
             nbytes = L.dpf_point_mesh_workspace_bytes(B, N)
             ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
-            check(L.dpf_point_mesh_distance(*_store_args(store), B, N, points.data_ptr(), slots.data_ptr(), max_faces, form,
+            check(L.dpf_point_mesh_distance(*store.abi_args(), B, N, points.data_ptr(), slots.data_ptr(), max_faces, form,
                                             dist.data_ptr(), face.data_ptr(), None if closest is None else closest.data_ptr(),
                                             ws.data_ptr(), nbytes, current_stream()), "point_mesh_distance")
     return dist, face, closest
@@ -229,7 +224,7 @@ def _launch_faces(points, store, slots, width, form, want_closest, want_area):
         with torch.cuda.device(dev):
             nbytes = L.dpf_mesh_point_workspace_bytes(B, width)
             ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
-            check(L.dpf_mesh_point_distance(*_store_args(store), B, N, points.data_ptr() if N else None, slots.data_ptr(), width, form,
+            check(L.dpf_mesh_point_distance(*store.abi_args(), B, N, points.data_ptr() if N else None, slots.data_ptr(), width, form,
                                             dist.data_ptr(), point.data_ptr(), None if closest is None else closest.data_ptr(),
                                             None if area is None else area.data_ptr(), ws.data_ptr(), nbytes, current_stream()),
                   "mesh_point_distance")

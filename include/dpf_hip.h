@@ -823,7 +823,7 @@ int dpf_point_mesh_distance_grad(int B, int N, const float *points, const float 
  * closest point on the face to that point; area (B, W) fp32, optional = the face's area.
  *   Pair arithmetic: the sequence stated above, defined once (csrc/pm_pair.h) and included by both translation units; a pair has
  *     the same bits in both directions.
- *   Area: dpf_mesh_cdf_build's fp32 sequence (e1 = p2 - p0, e2 = p2 - p1, cross product as a product minus a product,
+ *   Area: dpf_mesh_cdf_build's fp32 sequence, csrc/mesh_store.h's (e1 = p2 - p0, e2 = p2 - p1, cross product a product minus a product,
  *     sqrt((c0*c0 + c1*c1) + c2*c2) / 2, nothing fused), 0 where that build counts the face as 0 (a non-finite area).
  *   Ties: among points of equal fp32 distance the LOWEST point index is reported -- the minimum of (distance bits << 32 | point
  *     index) as unsigned 64-bit keys.  A non-finite point is skipped: it is never a face's nearest.

@@ -154,6 +154,36 @@ def test_forms_batches_and_runs_agree_bit_for_bit(PM, store):
         assert same([x[b] for x in twice], [x[0] for x in alone[1]]), b
 
 
+# ---- 2b. past the slots of one launch ------------------------------------------------------------------------------------------------
+EDGE_SLOTS = (0, 32767, 32768)
+
+
+def test_slots_past_one_launch(PM, DS):
+    """B = 32 769 slots of one point each, all naming the one-triangle mesh: one more than a launch holds along y
+    (dispatch::MAX_SLOTS = 32 768), so the last slot is served by a second launch -- of the search in both forms and of the
+    backward.  The last slot of the first launch, the first of the second and slot 0 equal, bit for bit, a call with that point
+    alone.  The limit along x (2^22 workgroups) would need about 10^9 items: tests/test_chunk_dispatch_cpu.py crosses it on the
+    host with small limits instead."""
+    one = DS.MeshStore(*MC.pack([MESHES["one"]]), device=dev())
+    B = EDGE_SLOTS[-1] + 1
+    pts = np.random.RandomState(43).standard_normal((B, 1, 3)).astype(np.float32)
+    for form in FORMS:
+        got = run(PM, one, pts, [0] * B, form)
+        assert got[0].shape == (B, 1) and np.isfinite(got[0]).all() and (got[1] == 0).all()
+        for b in EDGE_SLOTS:
+            assert same([x[b] for x in got], [x[0] for x in run(PM, one, pts[b:b + 1], [0], form)]), (b, form)
+    g = np.random.RandomState(44).standard_normal((B, 1)).astype(np.float32)
+
+    def grad(sel):
+        p = tensor(pts[sel]).requires_grad_(True)
+        dist, _ = PM.mesh_point_distance(p, one, [0] * len(pts[sel]))
+        return torch.autograd.grad(dist, p, tensor(g[sel]))[0].cpu().numpy()
+    whole = grad(slice(None))
+    assert np.isfinite(whole).all() and (whole != 0).any(axis=(1, 2)).all()
+    for b in EDGE_SLOTS:
+        assert np.array_equal(bits(whole[b]), bits(grad(slice(b, b + 1))[0])), b
+
+
 # ---- 3. ties ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("form", FORMS)
 def test_ties_report_the_lowest_point(PM, store, form):

@@ -211,6 +211,23 @@ def test_drawn_faces_follow_the_areas(DS, store, meshes):
     assert np.isfinite(pts).all() and np.abs(pts).max() <= 0.5
 
 
+def test_slots_past_one_launch(DS):
+    """B = 32 769 slots of one sample each, all naming the one-triangle mesh: one more than a launch of the sampler holds along y
+    (dispatch::MAX_SLOTS = 32 768), so the last slot is served by a second launch.  The last slot of the first launch, the first
+    of the second and slot 0 equal, bit for bit, a call with those variates alone.  The limit along x (2^22 workgroups) would
+    need about 10^9 items: tests/test_chunk_dispatch_cpu.py crosses it on the host with small limits instead."""
+    one = DS.MeshStore(*MC.pack([MC.one_face()]), device=dev())
+    B = 32769
+    var = DS.host_variates(11, 2, B, 1)
+    got = DS.sample_clouds(one, [0] * B, 1, variates=var, return_faces=True)
+    assert got["cloud"].shape == (B, 3, 1) and torch.isfinite(got["cloud"]).all() and bool((got["faces"] == 0).all())
+    for b in (0, 32767, 32768):
+        alone = DS.sample_clouds(one, [0], 1, variates=tuple(x[b:b + 1] for x in var), return_faces=True)
+        for name in ("cloud", "faces"):
+            assert torch.equal(got[name][b], alone[name][0]), (name, b)
+        assert np.array_equal(bits(got["cloud"][b]), bits(alone["cloud"][0])), b
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # 5. the distribution of a mesh depends on that mesh only
 # ---------------------------------------------------------------------------------------------------------------
