@@ -132,6 +132,8 @@ SIGNATURES = {
     "dpf_emd_exact": (_i, [_i, _i, _vp, _l, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dpf_pairwise_emd_exact": (_i, [_i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dpf_emd_exact_grad": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dpf_fps_max_points": (_i, []),
+    "dpf_fps": (_i, [_i, _i, _vp, _l, _l, _l, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "dpf_version": (ctypes.c_char_p, []),
 }
 

@@ -338,5 +338,32 @@ inline EEForm ee_form(int n, int force) {
     return {EEKernel::Resident, threads, 36};
 }
 
+// ---- farthest-point sampling (fps.hip) ------------------------------------------------------------------------------------------
+constexpr int FPS_MAX_POINTS = 8192;    // points per cloud: 12 bytes a point in LDS, 96 KB of the CU's 160
+constexpr int FPS_WAVE_MAX = 512;       // the one-wave form's: 8 points a lane
+constexpr int FPS_QUAD_MAX = 8192;      // the four-wave form's: 32 points a thread (198 registers, one wave per SIMD)
+constexpr int FPS_QUAD_UPTO = 4096;     // by size: four waves up to here, sixteen above
+// Wave: 64 threads, no barrier in a round; Quad: 256 threads, one wave per SIMD; Full: 1024 threads, four waves per SIMD.  ppt: the
+// points a thread keeps in registers, the lowest power of two with threads * ppt >= n.  force: 0 by size, 1 Wave, 2 Quad, 3 Full;
+// Unserved: n outside 1..FPS_MAX_POINTS, a form forced past its limit, an unknown form.
+// By size (profiles/fps_forms.txt; us per round at B = 1 | ms per call at B = 1024 clouds, k = n):
+//   n =  256: Wave 0.341 | 0.101, Quad 0.451 | 0.158, Full 0.736 | 0.543    n =  512: Wave 0.395 | 0.232, Quad 0.443 | 0.342, Full 0.711 | 1.059
+//   n = 1024:                     Quad 0.473 | 0.790, Full 0.698 | 2.110    n = 4096:                     Quad 0.727 | 6.51,  Full 0.848 | 10.97
+//   n = 8192:                     Quad 1.175 | 38.8,  Full 1.133 | 37.4
+// One wave wins wherever it serves: a round without a barrier, and four times the clouds on a CU.  Sixteen waves pay a dearer
+// meeting (0.70 us a round with one point a thread) and win only where four waves would hold 32 points a thread.
+enum class FPSKernel { Wave, Quad, Full, Unserved };
+struct FPSForm { FPSKernel kernel; int threads, ppt; };
+inline FPSForm fps_form(int n, int force) {
+    if (n < 1 || n > FPS_MAX_POINTS || force < 0 || force > 3) return {FPSKernel::Unserved, 0, 0};
+    if ((force == 1 && n > FPS_WAVE_MAX) || (force == 2 && n > FPS_QUAD_MAX)) return {FPSKernel::Unserved, 0, 0};
+    const FPSKernel kernel = force == 1 ? FPSKernel::Wave : force == 2 ? FPSKernel::Quad : force == 3 ? FPSKernel::Full
+                             : n <= FPS_WAVE_MAX ? FPSKernel::Wave : n <= FPS_QUAD_UPTO ? FPSKernel::Quad : FPSKernel::Full;
+    const int threads = kernel == FPSKernel::Wave ? 64 : kernel == FPSKernel::Quad ? 256 : 1024;
+    int ppt = 1;
+    while (threads * ppt < n) ppt *= 2;
+    return {kernel, threads, ppt};
+}
+
 }  // namespace dispatch
 #endif  // DPF_DISPATCH_H

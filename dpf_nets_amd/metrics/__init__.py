@@ -1,2 +1,3 @@
 from .point_mesh import point_mesh_distance, surface_accuracy   # noqa: F401
 from .point_mesh import mesh_point_distance, surface_completeness, surface_chamfer   # noqa: F401
+from .fps import farthest_point_sample   # noqa: F401

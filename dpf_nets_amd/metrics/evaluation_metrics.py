@@ -127,7 +127,18 @@ def _pairwise_matrices(clouds1, clouds2, batch_size, emd="approx"):
     return pairwise_CD(clouds1, clouds2, bs=batch_size), emd_matrix(clouds1, clouds2, bs=batch_size)
 
 
-def compute_all_metrics(sample_pcs, ref_pcs, batch_size, accelerated_cd=False, emd="approx"):
+def _reduce_to(clouds, n_points, name):
+    """the n_points farthest-point samples of every cloud, from index 0 (metrics/fps.py)"""
+    from .fps import farthest_point_sample
+    if not (isinstance(n_points, int) and not isinstance(n_points, bool)) or n_points < 1:
+        raise ValueError("n_points must be a positive integer or None, got %r" % (n_points,))
+    if n_points > clouds.shape[1]:
+        raise ValueError("n_points = %d exceeds the %d points of %s" % (n_points, clouds.shape[1], name))
+    with torch.no_grad():
+        return farthest_point_sample(clouds.float(), n_points)
+
+
+def compute_all_metrics(sample_pcs, ref_pcs, batch_size, accelerated_cd=False, emd="approx", n_points=None):
     """The generation metrics of the reference (:172-200): MMD and COV (lgan_mmd_cov) from the (sample, reference) matrices
     and 1-NN accuracy (knn, k = 1) from those plus the (reference, reference) and (sample, sample) matrices, for Chamfer and
     approximate EMD.  Keys "lgan_mmd-CD", "lgan_cov-CD", "lgan_mmd_smp-CD", the same for EMD, "1-NN-CD-acc_t",
@@ -135,7 +146,13 @@ def compute_all_metrics(sample_pcs, ref_pcs, batch_size, accelerated_cd=False, e
     as (reference, sample) and transposed for lgan_mmd_cov, and approx-EMD is not symmetric in its operands.  `batch_size`
     bounds the pairs per launch; `accelerated_cd` is accepted and ignored (module docstring).  No autograd (pairwise_EMD).
     emd="exact" builds the three EMD matrices from pairwise_EMD_exact (the optimal matching; same keys); the default is the
-    reference's approximate matcher."""
+    reference's approximate matcher.
+    n_points: None -- the clouds as they are; an integer -- both sets are first reduced to that many points per cloud by
+    farthest-point sampling from index 0 (farthest_point_sample: the subset that covers a cloud best for its size), which brings
+    sets of different cloud sizes to the common size the EMD halves need and cuts the cost of the three EMD matrices; raises
+    ValueError if it exceeds either set's cloud size."""
+    if n_points is not None:
+        sample_pcs, ref_pcs = _reduce_to(sample_pcs, n_points, "sample_pcs"), _reduce_to(ref_pcs, n_points, "ref_pcs")
     results = {}
     M_rs_cd, M_rs_emd = _pairwise_matrices(ref_pcs, sample_pcs, batch_size, emd)
     for metric, M in (("CD", M_rs_cd), ("EMD", M_rs_emd)):

@@ -908,6 +908,38 @@ int dpf_pairwise_emd_exact(int N1, int N2, int n, const float *clouds1, const fl
 int dpf_emd_exact_grad(int B, int n, const float *a, const float *b, const int *assignment, const int *inverse,
                        const float *grad_cost, float *grad_a, float *grad_b, dpf_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * Farthest-point sampling (csrc/fps.hip): the k points of a cloud of n that cover it best, chosen greedily -- what brings clouds of
+ * any size to the common size the matching metrics above need.  Not a port: the reference has no FPS.  tests/fps_ref.py restates all
+ * of this in numpy.
+ *   Input: xyz holds B clouds of n points, fp32, read in place through three strides counted in floats: coordinate a of point i of
+ *     cloud b is xyz[b * cloud_stride + i * point_stride + a * axis_stride].  (B, n, 3) point-major is (3n, 3, 1); (B, 3, N)
+ *     channel-major, the networks' layout, is (3N, 1, N); cloud_stride == 0 broadcasts one cloud.  1 <= k <= n <= the max_points
+ *     query's value = 8192, DPF_ENOSUP beyond; bad arguments (B < 0, n < 1, k < 1, k > n, a missing xyz or index, an unknown form)
+ *     return DPF_EINVAL; B == 0 launches nothing.  start: (B) int32, the first selection of every cloud, or NULL = 0 for every cloud.
+ *   Arithmetic: d(i, j) = (dx*dx + dy*dy) + dz*dz with dx = x_i - x_j and the same per axis, every fp32 operation rounded on its own
+ *     (no contraction).  d >= +0, and +inf where finite coordinates overflow; from finite input no NaN arises.
+ *   Selection: sel_0 = start[b], mind_0[i] = d(i, sel_0); for t >= 1 sel_t = the LOWEST index i that attains max_i mind_(t-1)[i],
+ *     and mind_t[i] = min(mind_(t-1)[i], d(i, sel_t)).
+ *   Outputs per cloud: index (B, k) int32 = sel_t; radius2 (B, k) fp32, optional (NULL: not written), radius2[t] = max_i mind_t[i],
+ *     the squared covering radius of the first t + 1 selections: it never increases with t, radius2[k-1] is the squared one-sided
+ *     Hausdorff distance from the cloud to its subset, and it is 0 from the point where every distinct position has been taken.  Once
+ *     radius2 is 0 every mind is 0 and the rule above keeps selecting index 0: a caller who asks for more points than the cloud has
+ *     distinct positions gets repeats of point 0.  status (B) int32, optional: 0 = done; DPF_FPS_REFUSED = a non-finite coordinate
+ *     among the cloud's n points or a start outside [0, n), and then index is -1 and radius2 NaN for that cloud.  Finite coordinates
+ *     whose squared distance overflows to +inf are NOT refused: the rule is well defined on them (+inf is an ordinary maximum).
+ *   Determinism: every output is bit-identical from run to run and depends on nothing but the cloud's own n points, k and start[b]
+ *     -- not on the batch, the strides, the form or the launch shape.  One cloud's refusal touches no other cloud.
+ *   form: 0 = by size (dispatch.h: fps_form: one wave up to 512 points, four waves up to 4096, sixteen above); 1 = one wave per
+ *     cloud, n <= 512; 2 = a workgroup of four waves; 3 = of sixteen waves (the points per thread are a compile-time parameter of
+ *     the kernel, a power of two).  A form forced past its limit returns DPF_ENOSUP, an unknown form DPF_EINVAL.
+ *   One workgroup per cloud (the cloud index on grid.x: B may exceed 65535), one launch, the caller's stream, no synchronisation, no
+ *     workspace, no memset nodes.  Every loop runs over n, over k or over a fixed number of waves: no input makes a launch spin. */
+#define DPF_FPS_REFUSED (-1)
+int dpf_fps_max_points(void);
+int dpf_fps(int B, int n, const float *xyz, long cloud_stride, long point_stride, long axis_stride, int k, const int *start, int form,
+            int *index, float *radius2, int *status, dpf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
