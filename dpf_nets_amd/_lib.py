@@ -134,6 +134,12 @@ SIGNATURES = {
     "dpf_emd_exact_grad": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dpf_fps_max_points": (_i, []),
     "dpf_fps": (_i, [_i, _i, _vp, _l, _l, _l, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "dpf_swd_max_points": (_i, []),
+    "dpf_swd_tables": (_i, [_i, _i, _vp, _l, _l, _l, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "dpf_swd_pairs": (_i, [_i, _i, _i, _vp, _vp, _l, _vp, _vp, _l, _i, _vp, _vp]),
+    "dpf_swd_pairwise": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "dpf_swd_grad_workspace_bytes": (_sz, [_i, _i, _i]),
+    "dpf_swd_grad": (_i, [_i, _i, _i] + [_vp] * 10 + [_vp, _sz, _vp]),
     "dpf_version": (ctypes.c_char_p, []),
 }
 

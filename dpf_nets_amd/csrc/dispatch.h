@@ -365,5 +365,33 @@ inline FPSForm fps_form(int n, int force) {
     return {kernel, threads, ppt};
 }
 
+// ---- sliced Wasserstein: the per-(cloud, direction) sort (swd.hip) ---------------------------------------------------------------
+constexpr int SWD_MAX_POINTS = 8192;    // keys per sort: 8 bytes a key in LDS, 64 KB of the CU's 160
+constexpr int SWD_WAVE_MAX = 512;       // the one-wave form's: 8 keys a lane, no LDS and no barrier in the sort
+constexpr int SWD_QUAD_MAX = 8192;      // the four-wave form's: 32 keys a thread
+constexpr int SWD_QUAD_UPTO = 2048;     // by size: four waves up to here, sixteen above
+// Wave: 64 threads; Quad: 256; Full: 1024.  kpt: the keys a thread keeps in registers, the lowest power of two with
+// threads * kpt >= n -- the bitonic network sorts threads * kpt keys, so one instantiation serves one power-of-two class of n.
+// force: 0 by size, 1 Wave, 2 Quad, 3 Full; Unserved: n outside 1..SWD_MAX_POINTS, a form forced past its limit, an unknown form.
+// By size (profiles/swd_forms.txt, the rows "the sort by form": us per sort with 8192 sorts in flight | us for one sort alone):
+//   n =  512: Wave 0.013 | 49.4, Quad 0.016 | 28.8, Full 0.047 | 32.1     n = 1024: Quad 0.026 | 40.1, Full 0.048 | 32.6
+//   n = 2048: Quad 0.050 | 62.4, Full 0.072 | 42.5                        n = 4096: Quad 0.124 | 110.0, Full 0.123 | 60.1
+//   n = 8192: Quad 0.438 | 213.0, Full 0.238 | 100.6
+// The thresholds follow the throughput column, the one a table build of many sorts pays: one wave wins wherever it serves (no
+// LDS pass, no barrier, four times the sorts on a CU); four waves win up to 2048; at 4096 the two tie in throughput and sixteen
+// waves halve the latency; at 8192 sixteen waves win by 1.8 (four waves hold 32 keys a thread there).
+enum class SWDKernel { Wave, Quad, Full, Unserved };
+struct SWDForm { SWDKernel kernel; int threads, kpt; };
+inline SWDForm swd_form(int n, int force) {
+    if (n < 1 || n > SWD_MAX_POINTS || force < 0 || force > 3) return {SWDKernel::Unserved, 0, 0};
+    if ((force == 1 && n > SWD_WAVE_MAX) || (force == 2 && n > SWD_QUAD_MAX)) return {SWDKernel::Unserved, 0, 0};
+    const SWDKernel kernel = force == 1 ? SWDKernel::Wave : force == 2 ? SWDKernel::Quad : force == 3 ? SWDKernel::Full
+                             : n <= SWD_WAVE_MAX ? SWDKernel::Wave : n <= SWD_QUAD_UPTO ? SWDKernel::Quad : SWDKernel::Full;
+    const int threads = kernel == SWDKernel::Wave ? 64 : kernel == SWDKernel::Quad ? 256 : 1024;
+    int kpt = 1;
+    while (threads * kpt < n) kpt *= 2;
+    return {kernel, threads, kpt};
+}
+
 }  // namespace dispatch
 #endif  // DPF_DISPATCH_H

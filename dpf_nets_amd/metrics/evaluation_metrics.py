@@ -138,7 +138,7 @@ def _reduce_to(clouds, n_points, name):
         return farthest_point_sample(clouds.float(), n_points)
 
 
-def compute_all_metrics(sample_pcs, ref_pcs, batch_size, accelerated_cd=False, emd="approx", n_points=None):
+def compute_all_metrics(sample_pcs, ref_pcs, batch_size, accelerated_cd=False, emd="approx", n_points=None, swd=None):
     """The generation metrics of the reference (:172-200): MMD and COV (lgan_mmd_cov) from the (sample, reference) matrices
     and 1-NN accuracy (knn, k = 1) from those plus the (reference, reference) and (sample, sample) matrices, for Chamfer and
     approximate EMD.  Keys "lgan_mmd-CD", "lgan_cov-CD", "lgan_mmd_smp-CD", the same for EMD, "1-NN-CD-acc_t",
@@ -150,7 +150,12 @@ def compute_all_metrics(sample_pcs, ref_pcs, batch_size, accelerated_cd=False, e
     n_points: None -- the clouds as they are; an integer -- both sets are first reduced to that many points per cloud by
     farthest-point sampling from index 0 (farthest_point_sample: the subset that covers a cloud best for its size), which brings
     sets of different cloud sizes to the common size the EMD halves need and cuts the cost of the three EMD matrices; raises
-    ValueError if it exceeds either set's cloud size."""
+    ValueError if it exceeds either set's cloud size.
+    swd: None -- the keys and values above, nothing else; an integer L -- also "lgan_mmd-SWD", "lgan_cov-SWD", "lgan_mmd_smp-SWD"
+    and "1-NN-SWD-acc_t" / "-acc_f" / "-acc" from three pairwise_SWD matrices (metrics/sliced.py: the sliced 2-Wasserstein distance
+    with L directions of seed 0), in the same orientation, computed after n_points has been applied."""
+    if swd is not None and (not isinstance(swd, int) or isinstance(swd, bool) or swd < 1):
+        raise ValueError("swd must be a positive number of directions or None, got %r" % (swd,))
     if n_points is not None:
         sample_pcs, ref_pcs = _reduce_to(sample_pcs, n_points, "sample_pcs"), _reduce_to(ref_pcs, n_points, "ref_pcs")
     results = {}
@@ -161,6 +166,12 @@ def compute_all_metrics(sample_pcs, ref_pcs, batch_size, accelerated_cd=False, e
     M_ss_cd, M_ss_emd = _pairwise_matrices(sample_pcs, sample_pcs, batch_size, emd)
     for metric, (M_rr, M_rs, M_ss) in (("CD", (M_rr_cd, M_rs_cd, M_ss_cd)), ("EMD", (M_rr_emd, M_rs_emd, M_ss_emd))):
         results.update({"1-NN-%s-%s" % (metric, k): v for k, v in knn(M_rr, M_rs, M_ss, 1, sqrt=False).items() if 'acc' in k})
+    if swd is not None:
+        from .sliced import pairwise_SWD
+        M_rs, M_rr, M_ss = (pairwise_SWD(a.float(), b.float(), n_directions=swd, seed=0)
+                            for a, b in ((ref_pcs, sample_pcs), (ref_pcs, ref_pcs), (sample_pcs, sample_pcs)))
+        results.update({"%s-SWD" % k: v for k, v in lgan_mmd_cov(M_rs.t()).items()})
+        results.update({"1-NN-SWD-%s" % k: v for k, v in knn(M_rr, M_rs, M_ss, 1, sqrt=False).items() if 'acc' in k})
     return results
 
 

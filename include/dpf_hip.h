@@ -940,6 +940,58 @@ int dpf_fps_max_points(void);
 int dpf_fps(int B, int n, const float *xyz, long cloud_stride, long point_stride, long axis_stride, int k, const int *start, int form,
             int *index, float *radius2, int *status, dpf_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * Sliced 2-Wasserstein distance (csrc/swd.hip): project two clouds on L directions, sort each projection, and the 1-D optimal
+ * transport of a direction is the rank-to-rank match -- a transport distance at O(L n log n) per CLOUD and O(L n) per PAIR, since the
+ * sort belongs to a cloud and not to a pair.  Not a port: the reference has no such metric.  tests/swd_ref.py restates all of this in
+ * numpy.
+ * dpf_swd_tables
+ *   Input: xyz holds B clouds of n points, fp32, read in place through three strides counted in floats, exactly as dpf_fps reads them
+ *     ((B, n, 3) is (3n, 3, 1); (B, 3, N) is (3N, 1, N); cloud_stride == 0 broadcasts one cloud).  dirs: (L, 3) fp32, dense; they are
+ *     NOT normalised here.  1 <= n <= the max_points query's value = 8192 (n need not be a power of two), DPF_ENOSUP beyond; L >= 1 and
+ *     B * L < 2^31; bad arguments (B < 0, n < 1, L < 1, B * L too large, a missing xyz, dirs or sorted, an unknown form) return
+ *     DPF_EINVAL; B == 0 launches nothing.
+ *   Projection: p(b, l, i) = ((x * tx + y * ty) + z * tz) + 0.0f with (tx, ty, tz) = dirs[l], every fp32 operation rounded on its own
+ *     (no contraction).  The final + 0.0f turns -0 into +0, so equal values have equal bits.
+ *   Order: order(b, l, .) is the permutation of 0..n-1 that sorts the keys (p, i) ascending -- the value compared as a float, the
+ *     LOWEST index first among equal values; sorted(b, l, r) = p(b, l, order(b, l, r)).
+ *   Outputs: sorted (B, L, n) fp32; order (B, L, n) int32, optional (NULL: not written -- the pair sums do not need it); status (B)
+ *     int32, optional: 0 or DPF_SWD_REFUSED.
+ *   Refusal: a cloud is refused when any of its 3n coordinates, any of the 3L direction components or any of its L * n projections is
+ *     not finite (overflow of finite input included).  Its L rows of sorted are then NaN and of order -1.  One cloud's refusal touches
+ *     no other cloud (a non-finite direction refuses every cloud: it is part of every cloud's projections).
+ *   Determinism: every output is bit-identical from run to run and depends on nothing but the cloud's own points and dirs -- not on
+ *     the batch, the strides, the form or the launch shape.
+ *   form: 0 = by size (dispatch.h: swd_form); 1 = one wave per sort, n <= 512; 2 = a workgroup of four waves; 3 = of sixteen waves
+ *     (the keys per thread are a compile-time parameter, a power of two).  A form forced past its limit returns DPF_ENOSUP.
+ *   One workgroup per (cloud, direction), one launch (one per 2^32 threads beyond that), the caller's stream, no synchronisation, no
+ *     workspace, no memset nodes.  Every loop is bounded by n, log n or L.
+ * dpf_swd_pairs / dpf_swd_pairwise read only sorted and status.  A table row is one cloud's (L, n) block.
+ *   sumsq = sum_l sum_r (double) fl32(sa(l, r) - sb(l, r))^2, accumulated in float64 (the order of the additions is the kernel's; the
+ *     result is within L * n * 2^-53 relative of the exact sum whatever it is).  Output float64: (B) for dpf_swd_pairs -- cloud
+ *     b * a_stride of table A against cloud b * b_stride of table B, strides in table rows, 0 broadcasts -- and (N1, N2) row-major for
+ *     dpf_swd_pairwise.  accumulate: 0 overwrites sumsq, 1 adds to what is there (one owner thread per pair, no atomics): a caller
+ *     can walk the directions in chunks and never hold more than a chunk of the tables.  A pair with a refused side gives NaN.
+ *     The distance is sumsq / (L * n), the Monte-Carlo SW2^2: no square root.  Bit-identical from run to run.
+ * dpf_swd_grad: the permutations are constants.  With g(l, i) = fl32(sa(l, r) - sb(l, r)) at r = the rank of point i of a in
+ *   direction l,  grad_a(b, i, axis) = fl32((double) grad_cost(b) * (2 / ((double) L * n)) * sum_l (double) g(l, i) * (double)
+ *   dirs(l, axis)), the sum in float64 in ascending l; grad_b is the same with the sign reversed, at the ranks of b's points.  grad_a,
+ *   grad_b: (B, n, 3) fp32 dense, either may be NULL (then its order may be too); grad_cost (B) fp32.  Refused pairs give 0.  No
+ *   atomics: g is scattered through order into the workspace ((B, L, n) fp32, dpf_swd_grad_workspace_bytes; the targets are a
+ *   permutation) and reduced over l per point.  B <= 65535.  Bit-identical from run to run.  No gradient for the directions. */
+#define DPF_SWD_REFUSED (-1)
+int dpf_swd_max_points(void);
+int dpf_swd_tables(int B, int n, const float *xyz, long cloud_stride, long point_stride, long axis_stride, int L, const float *dirs,
+                   int form, float *sorted, int *order, int *status, dpf_stream_t stream);
+int dpf_swd_pairs(int B, int L, int n, const float *sorted_a, const int *status_a, long a_stride, const float *sorted_b,
+                  const int *status_b, long b_stride, int accumulate, double *sumsq, dpf_stream_t stream);
+int dpf_swd_pairwise(int N1, int N2, int L, int n, const float *sorted1, const int *status1, const float *sorted2, const int *status2,
+                     int accumulate, double *sumsq, dpf_stream_t stream);
+size_t dpf_swd_grad_workspace_bytes(int B, int L, int n);
+int dpf_swd_grad(int B, int L, int n, const float *dirs, const float *sorted_a, const int *order_a, const int *status_a,
+                 const float *sorted_b, const int *order_b, const int *status_b, const float *grad_cost, float *grad_a, float *grad_b,
+                 void *workspace, size_t workspace_bytes, dpf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
