@@ -297,6 +297,15 @@ def _emd_exact_workspace(pairs, n, dev):
     return torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev), nbytes
 
 
+def _emd_exact_normalise(cost, n):
+    """cost <- fl32(cost / n), the correctly rounded fp32 quotient, in place.  Not cost.div_(n): for a Python scalar torch multiplies
+    by fl32(1 / n) on the device, an ulp off for some costs unless n is a power of two (tests/test_gpu_emd_exact_edges.py: 3 of 15
+    entries at n = 129).  In float64 the product with 1 / n is within 2^-52 (relative) of the quotient, while the quotient of a
+    float32 by an integer n < 2^14 is never closer than 2^-38 to the midpoint of two float32 neighbours (the difference is a
+    non-zero integer over 2 n 2^k): rounding the float64 result to float32 gives the quotient's own float32 rounding."""
+    cost.copy_(cost.double().div_(float(n)))
+
+
 class EMDExactFunction(torch.autograd.Function):
     """cost (B,) of the optimal matching as ONE autograd node: forward = one dpf_emd_exact launch, the assignment and its inverse
     kept for the backward, which is one dpf_emd_exact_grad launch for the inputs that need a gradient (the assignment is a constant,
@@ -322,7 +331,7 @@ class EMDExactFunction(torch.autograd.Function):
             cost.zero_(); qcost.zero_(); status.zero_()
         ctx.scale = 1.0 / float(n) if normalise and n > 0 else 1.0
         if normalise and n > 0:
-            cost.div_(float(n))                                    # (emd_approx's fp32 division)
+            _emd_exact_normalise(cost, n)
         ctx.save_for_backward(sample, ref)
         ctx.assignment, ctx.inverse = assignment, inverse          # indices ride on ctx, as in NNDistanceFunction
         ctx.mark_non_differentiable(assignment, qcost, status)
@@ -408,7 +417,7 @@ def pairwise_EMD_exact(clouds1, clouds2, bs=512, shard_rows=False, bits=20, max_
                 check(lib().dpf_pairwise_emd_exact(nr, N2, n, clouds1[r0].data_ptr(), clouds2.data_ptr(), int(bits), int(max_rounds), 0,
                                                    qcost.data_ptr(), emds[r0 - lo].data_ptr(), status[r0 - lo].data_ptr(),
                                                    ws.data_ptr(), nbytes, current_stream()), "pairwise_emd_exact")
-        emds.div_(float(n))                                     # (the fp32 division of emd_exact, in place)
+        _emd_exact_normalise(emds, n)                           # (the division of emd_exact, in place)
         _emd_exact_warn(status, "pairwise_EMD_exact")
     if shard_rows:
         from .. import distributed as D

@@ -861,8 +861,8 @@ int dpf_mesh_point_distance_grad(int B, int N, long max_faces, const float *poin
  *     (frexp) and s = 2^(bits - 1 - ex); the integer cost of the pair of points (i, j) is
  *         c_ij = rint(sqrt((dx*dx + dy*dy) + dz*dz) * s),   d = a_i - b_j per axis,
  *     every fp32 operation rounded on its own (no contraction), the square root correctly rounded, the product with s exact, rint
- *     to nearest even; 0 <= c_ij < 2^bits.  bits in 1..24 (the Python default is 20).  Scaling both clouds by a power of two
- *     changes no c_ij.
+ *     to nearest even; 0 <= c_ij < 2^bits (d < sqrt(3) * E and E * s < 2^(bits - 1); at bits == 1 alone a diagonal of the extent's box
+ *     can round up to c_ij == 2).  bits in 1..24 (the Python default is 20).  Scaling both clouds by a power of two changes no c_ij.
  *   Refused pairs (status DPF_EMD_EXACT_REFUSED): any non-finite coordinate; E not finite; E * E not a normal fp32 number; 3 * (E * E)
  *     not finite (a diagonal's square could overflow).
  *   The auction minimises sum_i c_i,sigma(i) over permutations sigma.  Point i of a values object j (point j of b) at

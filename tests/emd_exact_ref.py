@@ -60,7 +60,8 @@ def cost_matrix(a, b, bits=BITS):
     if s == 0:
         return 0, np.zeros((n, n), np.int64), s
     c = np.rint((dist_matrix(a, b) * s).astype(F32)).astype(np.int64)
-    assert c.max() < (1 << bits)
+    # d < sqrt(3) E and E s < 2^(bits - 1): below 2^bits from 2 bits on; at bits == 1 a diagonal of the extent's box can round to 2
+    assert c.max() < (1 << bits) or (bits == 1 and c.max() == 2)
     return 0, c, s
 
 
@@ -154,10 +155,30 @@ def grad64(a, b, assignment, g):
 
 # ---- the case list of the GPU test (and of the K measurement on the CPU) ------------------------------------------------------
 KINDS = ("gauss", "collapsed", "collinear", "lattice", "perm", "shift", "same")
+# the kinds of tests/test_gpu_emd_exact_edges.py only (KINDS is the parametrisation of the first suite and of the K measurement)
+EDGE_KINDS = ("jitter", "point", "point_signed")
+JITTER = 2.0          # the noise of "jitter" in standard deviations of the cloud: the largest of the amplitudes tried at which the
+                      # oracle still solves 4 096 and 4 097 points in under ten seconds (tests/test_gpu_emd_exact_edges.py has the table)
+
+
+def scaling_edges(a, b, bits=BITS):
+    """(lo, hi): the smallest and the largest k at which the pair scaled by 2^k (in float32) is still served, not refused.  Below lo
+    E * E is no normal float32; above hi 3 * (E * E), or a coordinate, overflows."""
+    def served(k):
+        f = np.ldexp(F32(1), k)
+        with np.errstate(over="ignore"):
+            return grid_scale((np.asarray(a, F32) * f).astype(F32), (np.asarray(b, F32) * f).astype(F32), bits)[0] == 0
+    assert served(0)
+    lo = hi = 0
+    while lo > -200 and served(lo - 1):
+        lo -= 1
+    while hi < 200 and served(hi + 1):
+        hi += 1
+    return lo, hi
 
 
 def make_case(kind, n, seed):
-    """(a, b, extra): two (n, 3) float32 clouds; extra: the permutation of "perm", the offset of "shift", else None"""
+    """(a, b, extra): two (n, 3) float32 clouds; extra: the permutation of "perm" and "jitter", the offset of "shift", else None"""
     rng = np.random.RandomState(seed)
     extra = None
     a = rng.randn(n, 3).astype(F32)
@@ -184,6 +205,20 @@ def make_case(kind, n, seed):
         b = (a + extra).astype(F32)
     elif kind == "same":
         b = a.copy()
+    elif kind == "jitter":                                           # a permuted copy moved by a little noise: the matching is mostly
+        extra = rng.permutation(n).astype(np.int32)                  # the permutation, and where it is not, objects change hands
+        b = np.empty_like(a)
+        b[extra] = a
+        b = (b + rng.randn(n, 3).astype(F32) * F32(JITTER)).astype(F32)
+    elif kind == "point":                                            # every point of both clouds the same: E == 0
+        a = np.repeat(a[:1], n, 0)
+        b = a.copy()
+    elif kind == "point_signed":                                     # the same with zeros of both signs: -0.0 == +0.0, E == 0
+        a = np.repeat(a[:1], n, 0)
+        a[:, 1] = F32(0)
+        b = a.copy()
+        a[0::2, 1] = F32(-0.0)
+        b[1::3, 1] = F32(-0.0)
     else:
         raise ValueError(kind)
     return np.ascontiguousarray(a), np.ascontiguousarray(b), extra

@@ -14,26 +14,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 import emd_exact_ref as R                                                                   # noqa: E402
+from emd_exact_common import U, check_pair, clouds, dev, run, same_bits                     # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 SIZES = (1, 2, 63, 64, 65, 256)
-K_CAP = 1.25                                    # grid steps per point (tests/test_emd_exact_ref_cpu.py)
 _ORACLE, _DEVICE = {}, {}
-
-
-def dev():
-    return torch.device("cuda", 0)
-
-
-def U():
-    from dpf_nets_amd.networks import utils
-    return utils
-
-
-def clouds(kind, n, B=3):
-    cases = [R.make_case(kind, n, 100 * n + k) for k in range(B)]
-    return np.stack([c[0] for c in cases]), np.stack([c[1] for c in cases]), [c[2] for c in cases]
 
 
 def oracle(kind, n, B=3):
@@ -44,41 +30,12 @@ def oracle(kind, n, B=3):
     return _ORACLE[key]
 
 
-def run(a, b, **kw):
-    """numpy (B, n, 3) pair -> numpy cost, assignment, qcost, status"""
-    out = U().emd_exact_full(torch.from_numpy(a).to(dev()), torch.from_numpy(b).to(dev()), **kw)
-    return tuple(t.detach().cpu().numpy() for t in out)
-
-
 def device(kind, n, B=3):
     key = (kind, n, B)
     if key not in _DEVICE:
         a, b, _ = clouds(kind, n, B)
         _DEVICE[key] = run(a, b)
     return _DEVICE[key]
-
-
-def same_bits(x, y):
-    def raw(v):
-        return np.ascontiguousarray(np.atleast_1d(np.asarray(v))).view(np.uint8)
-    return all(np.array_equal(raw(p), raw(q)) for p, q in zip(x, y))
-
-
-def check_pair(a, b, o, cost, asg, qcost, status, tag):
-    """assertions 1-5 of one solved pair"""
-    n = a.shape[0]
-    c64 = R.cost64(a, b, asg)
-    q = 1.0 / float(o["s"]) if o["s"] else 0.0
-    print(tag, "status", status, "oracle rounds", o["rounds"], "qcost", qcost, o["qcost"], "cost", cost, c64,
-          "rel", abs(float(cost) - c64) / max(c64, 1e-300), "K", (c64 - R.cost64(a, b, o["assignment"])) / (n * q) if q else 0.0)
-    assert status >= 0, tag
-    assert sorted(asg.tolist()) == list(range(n)), tag                                     # 1
-    assert int(qcost) == o["qcost"], tag                                                    # 2
-    assert int(qcost) == int(o["c"][np.arange(n), asg].sum()), tag                          # 3
-    assert abs(float(cost) - c64) <= (n + 8) * 2.0 ** -24 * c64, tag                        # 4
-    assert c64 <= R.cost64(a, b, o["assignment"]) + K_CAP * n * q, tag                      # 5
-    # the tie rules fix the outcome: the oracle's matching and its number of rounds
-    assert np.array_equal(asg, o["assignment"]) and int(status) == o["rounds"], tag
 
 
 @pytest.mark.parametrize("n", SIZES)
