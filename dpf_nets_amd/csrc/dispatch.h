@@ -393,5 +393,20 @@ inline SWDForm swd_form(int n, int force) {
     return {kernel, threads, kpt};
 }
 
+// ---- k nearest neighbours (knn.hip) ------------------------------------------------------------------------------------------------
+constexpr int KNN_MAX_K = 32;           // the largest list a lane keeps in registers: 64 VGPRs of (distance, index)
+constexpr int KNN_WG_QUERIES = 256;     // queries of a workgroup: 4 waves, one query per lane
+constexpr int KNN_TILE = 256;           // candidates per LDS tile (3 KB, structure of arrays)
+constexpr int KNN_QUEUE = 16;           // deferred candidates per lane (8 bytes each: 32 KB of LDS a workgroup)
+// kcap: the list capacity the kernel is instantiated for, 4 | 8 | 16 | 32; it serves k <= kcap and its outputs do not depend on it.
+// force: 0 = the smallest capacity >= k (the insertion chain costs 5 instructions per slot, so a larger one only costs); 1..4 force
+// capacity 4, 8, 16, 32.  Unserved (kcap 0): k outside 1..KNN_MAX_K, a forced capacity below k, an unknown form.
+struct KNNForm { int kcap; };
+inline KNNForm knn_form(int k, int force) {
+    if (k < 1 || k > KNN_MAX_K || force < 0 || force > 4) return {0};
+    if (force) return {(4 << (force - 1)) >= k ? 4 << (force - 1) : 0};
+    return {k <= 4 ? 4 : k <= 8 ? 8 : k <= 16 ? 16 : 32};
+}
+
 }  // namespace dispatch
 #endif  // DPF_DISPATCH_H

@@ -992,6 +992,42 @@ int dpf_swd_grad(int B, int L, int n, const float *dirs, const float *sorted_a, 
                  const float *sorted_b, const int *order_b, const int *status_b, const float *grad_cost, float *grad_a, float *grad_b,
                  void *workspace, size_t workspace_bytes, dpf_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * k nearest neighbours (csrc/knn.hip): for every query point the k points of its slot's cloud that are nearest to it, with their
+ * squared distances, ascending -- the neighbourhood a spacing statistic, a repulsion term or a local feature needs, without the
+ * (B, n, m) distance tensor.  Not a port: the reference has no point-level k-NN.  tests/knn_ref.py restates all of this in numpy.
+ *   Input: query holds B sets of n points and cloud B sets of m points, fp32, each read in place through three strides counted in
+ *     floats, exactly as dpf_fps reads a cloud: coordinate a of point i of slot b is p[b * cloud_stride + i * point_stride + a *
+ *     axis_stride].  (B, n, 3) point-major is (3n, 3, 1); (B, 3, N) channel-major is (3N, 1, N); a cloud stride of 0 broadcasts one
+ *     set over the batch.  query and cloud may be the same memory (a self-search); neither is written.
+ *   Arithmetic: d(i, j) = (dx*dx + dy*dy) + dz*dz with dx = c_j.x - q_i.x and the same per axis, every fp32 operation rounded on its
+ *     own (no contraction): dpf_nndistance's formula and bits.
+ *   Eligible candidates of query i: every j in [0, m); with exclude_same_index != 0 all of them but j == i.  The exclusion goes by
+ *     INDEX, not by distance: it is meant for a self-search, and a duplicate of the query at another index stays a neighbour at
+ *     distance 0.  (A query with i >= m has nothing to exclude.)
+ *   Result: the k eligible candidates with the smallest key (d, j), in ascending key order -- equal distances are ordered by the
+ *     LOWEST index first, among the listed ones and at the cut after the k-th.  dist (B, n, k) fp32 and index (B, n, k) int32, both
+ *     dense; status (B) int32, optional (NULL: not written): 0 or DPF_KNN_REFUSED.
+ *   Arguments: 1 <= k <= dpf_knn_max_k() = 32, DPF_ENOSUP above; k above the number of eligible candidates (m, or m - 1 with
+ *     exclude_same_index) returns DPF_EINVAL, as do B < 0, n < 1, m < 1, k < 1, a missing query, cloud, dist or index and an unknown
+ *     form; B == 0 launches nothing.
+ *   Refusal: a slot is refused when any coordinate of its n query points or its m cloud points is not finite or is larger in
+ *     magnitude than 2^61.  Within that bound |dx| <= 2^62 and d <= 3 * 2^124 < the largest fp32, so no distance overflows: +inf is
+ *     the value of an empty list slot and never ties with a real distance.  A refused slot gets dist NaN, index -1 and status
+ *     DPF_KNN_REFUSED; no other slot is touched (a refused broadcast set refuses every slot: it is part of each).
+ *   Determinism: every output is bit-identical from run to run and depends on nothing but the slot's own points, k and the flag --
+ *     not on B, the strides, the form or the launch shape.
+ *   form: 0 = by k (dispatch.h: knn_form: the smallest list capacity >= k); 1, 2, 3, 4 = a lane's list has capacity 4, 8, 16, 32 (a
+ *     compile-time parameter of the kernel).  A forced capacity below k returns DPF_ENOSUP.
+ *   One workgroup per 256 queries of a slot, one launch (cut by dispatch::chunk_grid past 32768 slots or 2^22 workgroups a slot), the
+ *     caller's stream, no synchronisation, no workspace, no atomics, no memset nodes.  Every loop runs over n, m, k or a fixed
+ *     queue depth: no input makes a launch spin. */
+#define DPF_KNN_REFUSED (-1)
+int dpf_knn_max_k(void);
+int dpf_knn(int B, int n, const float *query, long q_cloud_stride, long q_point_stride, long q_axis_stride, int m, const float *cloud,
+            long c_cloud_stride, long c_point_stride, long c_axis_stride, int k, int exclude_same_index, int form, float *dist,
+            int *index, int *status, dpf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
