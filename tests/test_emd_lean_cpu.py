@@ -48,9 +48,12 @@ def test_new_entries_are_exported_by_the_library():
 
 
 def _makefile_emd_rule():
+    """(FLAGS, the listing's compile line, the gate's line) of emd.o as make would run them (a dry run: every variable expanded)"""
+    if not shutil.which("make"):
+        pytest.skip("no make")
     mk = open(os.path.join(CSRC, "Makefile")).read()
     flags = re.search(r"^FLAGS := (.*)$", mk, flags=re.M).group(1)
-    rule = mk.split("emd.o:")[1].split("\n\n")[0].split("\n")[1:]
+    rule = subprocess.run(["make", "-n", "-B", "-C", CSRC, "emd.o"], capture_output=True, text=True, check=True, timeout=60).stdout.splitlines()
     compile_s = next(ln for ln in rule if " -S " in ln)
     gate = next(ln for ln in rule if "mfma_overlap_check.py" in ln)
     return flags, compile_s.strip(), gate.strip()

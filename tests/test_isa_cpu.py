@@ -71,12 +71,46 @@ def test_makefile_compiles_every_object_without_the_slp_vectoriser():
             assert "$(FLAGS)" in ln, ln
 
 
+_DRY_RUN = {}
+
+
+def _make_would_run():
+    """{object name: {"all": [...], "S": [...], "gate": [...], "more": [...], "c": [...]}}, each a list of argument lists: the commands
+    `make -n -B` prints for every object of the link line, in its order -- what make WOULD run, not the Makefile's text (no compiler needed)"""
+    if not shutil.which("make"):
+        pytest.skip("no make")
+    if not _DRY_RUN:
+        r = subprocess.run(["make", "-n", "-B", "-C", CSRC], capture_output=True, text=True, timeout=60)
+        assert r.returncode == 0, r.stderr[-2000:]
+        cmds = [ln.split() for ln in r.stdout.splitlines() if ln.strip()]
+        link = [c for c in cmds if "-shared" in c]
+        assert len(link) == 1, link
+        for obj in (t for t in link[0] if t.endswith(".o")):
+            x = obj[:-2]
+            mine = [c for c in cmds if c[-1] == x + ".s" or c[-2:] == ["-o", obj]]
+            _DRY_RUN[x] = {"all": mine, "S": [c for c in mine if "-S" in c], "c": [c for c in mine if "-c" in c],
+                           "gate": [c for c in mine if any(t.endswith("mfma_overlap_check.py") for t in c)],
+                           "more": [c for c in mine if c[0].startswith("python") and not any(t.endswith("mfma_overlap_check.py") for t in c)]}
+    return _DRY_RUN
+
+
+def _flag_set(cmd, *mode):
+    """a compile command's arguments without the ones that say WHAT it writes (-S --cuda-device-only -o X.s / -c -o X.o)"""
+    assert cmd[-2] == "-o" and cmd[-1] == mode[-1], cmd
+    return set(cmd[:-2]) - set(mode[:-1])
+
+
 def test_makefile_compiles_the_flow_stack_without_the_slp_vectoriser():
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    for target in ("flow.o", "flow_train.o"):
-        rule = mk[mk.index(target + ":"):]
-        assert "$(FLOWFLAGS)" in rule.split("\n\n")[0].split("\n", 2)[1], target
-    assert "FLOWFLAGS := -fno-slp-vectorize" in mk
+    """FLOWFLAGS is -fno-slp-vectorize and reaches the listing and the object of flow.o / flow_train.o (a dry run with FLOWFLAGS
+    replaced by a marker shows where it goes)"""
+    run = _make_would_run()
+    for x in ("flow", "flow_train"):
+        assert "-fno-slp-vectorize" in run[x]["S"][0] and "-fno-slp-vectorize" in run[x]["c"][0], x
+    r = subprocess.run(["make", "-n", "-B", "-C", CSRC, "flow.o", "flow_train.o", "FLOWFLAGS=-DFLOWFLAGS_GO_HERE"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr[-2000:]
+    compiles = [ln for ln in r.stdout.splitlines() if " -S " in ln or " -c " in ln]
+    assert len(compiles) == 4 and all("-DFLOWFLAGS_GO_HERE" in ln for ln in compiles), compiles
+    assert "FLOWFLAGS := -fno-slp-vectorize" in open(os.path.join(CSRC, "Makefile")).read()
 
 
 def test_no_packed_f32_and_no_scratch_in_the_flow_kernels(isa_flow, isa_flow_train):
@@ -146,16 +180,17 @@ def test_emd_matrix_passes_keep_the_mfma_destination_apart(tmp_path_factory):
     assert r.returncode == 0, r.stderr[-2000:]
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import mfma_overlap_check as chk
-    total, bad = chk.scan(str(out), require_register_c=True, no_scratch="emd_mfma_", no_packed="emd_mfma_")     # (what csrc/Makefile gates emd.o on)
-    assert total >= 20 and not bad, (total, bad[:3])
+    total, overlap, bad = chk.scan(str(out), require_register_c=True, no_scratch="emd_mfma_", no_packed="emd_mfma_")     # (what csrc/Makefile gates emd.o on)
+    assert total >= 20 and not overlap and not bad, (total, overlap[:3], bad[:3])
     text = out.read_text()
     for ln in text.splitlines():
         if "v_mfma_" in ln:
             assert re.search(r",\s*[va]\[\d+:\d+\]\s*$", ln), ln       # C is a register tuple, not the literal 0
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    rule = mk.split("emd.o:")[1].split("\n\n")[0]
-    assert "mfma_overlap_check.py --require-register-c --no-scratch emd_mfma_ --no-packed-f32 emd_mfma_ " in rule and rule.count(" emd.s") >= 2
-    assert rule.count("-fno-slp-vectorize") == 2              # the gated listing and the object are the same build
+    emd = _make_would_run()["emd"]
+    assert len(emd["S"]) == 1 and len(emd["gate"]) == 1 and len(emd["c"]) == 1, emd     # emd.s is compiled, gated, and only then emd.o
+    assert " --require-register-c --no-scratch emd_mfma_ --no-packed-f32 emd_mfma_ " in " ".join(emd["gate"][0]) and "--ignore-overlap" not in emd["gate"][0]
+    assert "-fno-slp-vectorize" in emd["S"][0] and "-fno-slp-vectorize" in emd["c"][0]
+    assert _flag_set(emd["S"][0], "-S", "--cuda-device-only", "emd.s") == _flag_set(emd["c"][0], "-c", "emd.o")     # the gated listing and the object are the same build
     # ... and none of the matrix-core kernels spills (r05: a build forced to 128 registers -- 40 to 123 spilled -- failed the
     # parity and repeat tests on the GPU, besides being 2 - 6 x slower)
     for name, body in _kernels(text).items():
@@ -202,21 +237,62 @@ kern_b: ; @kern_b
     assert chk.main(["--ignore-overlap", "--no-packed-with-mfma", "--no-packed-before-mfma", "--no-packed-low-from-high", str(p)]) == 1
 
 
-def test_makefile_gates_every_object_on_the_packed_fp32_rules():
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    gate = [ln for ln in mk.splitlines() if ln.startswith("GATE :=")]
-    assert len(gate) == 1 and all(o in gate[0] for o in ("--no-packed-with-mfma", "--no-packed-before-mfma", "--no-packed-low-from-high")), gate
-    rules = re.findall(r"^([\w%]+\.o): .*\n((?:\t.*\n)+)", mk, flags=re.M)
-    objs = re.search(r"^OBJS := (.*)$", mk, flags=re.M).group(1).split()
-    named = {t for t, _ in rules}
-    for t, body in rules:
-        if t.endswith(("_prof.o", "_ab.o")) or t not in set(objs) | {"%.o"}:
-            continue                                    # (profiling / ablation builds are scratch: nothing but libdpf_hip.so ships)
-        if t == "emd.o":
-            assert all(o in body for o in ("--no-packed-with-mfma", "--no-packed-before-mfma", "--no-packed-low-from-high")), body
-        else:
-            assert "$(call isa_gate," in body, (t, body)
-    assert "%.o" in named and "emd.o" in named
+PACKED_RULES = ["--no-packed-with-mfma", "--no-packed-before-mfma", "--no-packed-low-from-high"]
+# the kernels that keep their data in registers: object -> the --no-scratch PREFIX its gate carries
+NO_SCRATCH = {"emd": "emd_mfma_", "fps": "fps_kernel", "swd": "swd_sort_kernel", "knn": "knn_kernel", "encoder": "enc_kernel", "encoder_frozen": "ef_"}
+
+
+def _write(tmp_path, name, text):
+    p = tmp_path / name
+    p.write_text(text)
+    return str(p)
+
+
+def test_ignore_overlap_ignores_the_overlap_findings_and_nothing_else(tmp_path):
+    """--ignore-overlap (the library-wide gate) used to drop EVERY finding of scan(): a spilled fps_kernel built clean"""
+    chk = _checker()
+    gate = ["--ignore-overlap"] + PACKED_RULES
+    spilled = _write(tmp_path, "spilled.s", "fps_kernel: ; @fps_kernel\n\tscratch_load_dword v1, off\n.Lfunc_end0:\n")
+    assert chk.main(gate + ["--no-scratch", "fps_kernel", spilled]) == 1
+    assert chk.main(gate + ["--no-scratch", "other_kernel", spilled]) == 0
+    onto_a = _write(tmp_path, "onto_a.s", "kern: ; @kern\n\tv_mfma_f32_32x32x16_f16 v[2:17], v[2:5], v[70:73], v[20:35]\n.Lfunc_end0:\n")
+    assert chk.main(gate + [onto_a]) == 0 and chk.main(PACKED_RULES + [onto_a]) == 1
+    assert chk.main(gate + ["--no-scratch", "kern", onto_a]) == 0              # (no scratch there: still only the tolerated finding)
+    packed = _write(tmp_path, "packed.s", "emd_mfma_kern: ; @emd_mfma_kern\n\tv_pk_mul_f32 v[2:3], v[4:5], v[6:7]\n.Lfunc_end0:\n")
+    assert chk.main(gate + ["--no-packed-f32", "emd_mfma_", packed]) == 1
+    assert chk.main(gate + ["--no-packed-f32", "other_", packed]) == 0
+    literal_c = _write(tmp_path, "literal_c.s", "kern: ; @kern\n\tv_mfma_f32_32x32x16_f16 v[2:17], v[70:73], v[74:77], 0\n.Lfunc_end0:\n")
+    assert chk.main(gate + ["--require-register-c", literal_c]) == 1 and chk.main(gate + [literal_c]) == 0
+    total, overlap, other = chk.scan(onto_a, require_register_c=True, no_scratch="kern", no_packed="kern")
+    assert (total, len(overlap), other) == (1, 1, [])
+    total, overlap, other = chk.scan(spilled, no_scratch="fps_kernel")
+    assert (total, overlap, len(other)) == (0, [], 1)
+
+
+def test_makefile_gates_every_object_on_the_packed_fp32_rules(tmp_path):
+    """every object of the link line, from what make would run: one listing, ONE checker call on it with the three packed-fp32 rules
+    (and the object's own arguments), then the object -- compiled with the flags of the listing that was gated"""
+    chk = _checker()
+    run = _make_would_run()
+    assert len(run) >= 25 and set(NO_SCRATCH) <= set(run), sorted(run)
+    for x, cmds in run.items():
+        assert len(cmds["S"]) == 1 and len(cmds["gate"]) == 1 and len(cmds["c"]) == 1, (x, cmds)
+        s, gate, c = cmds["S"][0], cmds["gate"][0], cmds["c"][0]
+        assert "--cuda-device-only" in s and x + ".hip" in s and x + ".hip" in c, (s, c)
+        assert _flag_set(s, "-S", "--cuda-device-only", x + ".s") == _flag_set(c, "-c", x + ".o"), (s, c)     # the same build
+        assert gate[-1] == x + ".s" and all(o in gate for o in PACKED_RULES), gate
+        assert ("--ignore-overlap" in gate) == (x != "emd"), gate
+        prefixes = [gate[i + 1] for i, t in enumerate(gate) if t == "--no-scratch"]
+        assert prefixes == ([NO_SCRATCH[x]] if x in NO_SCRATCH else []), (x, gate)
+        for prefix in prefixes:                          # ... in a call that can fail on it: the call's own arguments refuse a spilled kernel
+            at = next(i for i, t in enumerate(gate) if t.endswith("mfma_overlap_check.py"))
+            spilled = _write(tmp_path, x + "_spilled.s", "_Z3%sxyz: ; @kernel\n\tscratch_load_dword v1, off\n.Lfunc_end0:\n" % prefix)
+            clean = _write(tmp_path, x + "_clean.s", "_Z3%sxyz: ; @kernel\n.Lfunc_end0:\n" % prefix)
+            assert chk.main(gate[at + 1:-1] + [spilled]) == 1 and chk.main(gate[at + 1:-1] + [clean]) == 0, gate
+        assert cmds["all"] == [s, gate] + cmds["more"] + [c], (x, cmds["all"])     # in this order, and nothing else
+    emd = run["emd"]["gate"][0]
+    assert "--require-register-c" in emd and emd[emd.index("--no-packed-f32") + 1] == "emd_mfma_", emd
+    assert [m[-2:] for m in run["flow"]["more"]] == [["../../tools/film_loads_check.py", "flow.s"]], run["flow"]
 
 
 def test_the_built_objects_hold_no_affected_packed_form():

@@ -4,15 +4,18 @@ r05: such an instruction ("v_mfma_f32_32x32x16_f16 v[2:17], v[70:73], v[2:5], 0"
 a source that dies there) produced results that differed from run to run on MI355X (csrc/emd.hip, pair_exponents).  A destination
 identical to source C is the normal accumulate form and is not reported.
 
-    python tools/mfma_overlap_check.py [--require-register-c] [--no-scratch PREFIX] file.s [...]
-        -> one line per offending instruction; exit status 1 if any
+    python tools/mfma_overlap_check.py [--ignore-overlap] [--require-register-c] [--no-scratch PREFIX] [--no-packed-f32 PREFIX]
+                                       [--no-packed-with-mfma] [--no-packed-before-mfma] [--no-packed-low-from-high] [--war] file.s [...]
+        -> one line per offending instruction; exit status 1 if any.  Every option but --ignore-overlap ADDS findings, and
+           --ignore-overlap takes away the overlapping destinations only: what another option finds always prints and always fails
     --require-register-c   also report MFMAs whose C operand is not a register tuple (the literal-0 form is the one the compiler
                            pairs with an overlapping destination)
     --no-scratch PREFIX    also fail if a kernel whose name contains PREFIX touches scratch memory (a spilled build of the
                            approx-EMD passes flickered too)
     --no-packed-f32 PREFIX r06: also fail if a kernel whose name contains PREFIX holds v_pk_{fma,mul,add}_f32 (the SLP vectoriser's
                            packed accumulations: see the next option; the approx-EMD passes keep none at all)
-    --ignore-overlap       count the overlapping destinations but do not fail on them (csrc/Makefile's gate for every object)
+    --ignore-overlap       count the overlapping destinations but do not fail on them (csrc/Makefile's gate for every object but
+                           emd.o); the scratch, packed-in-kernel and register-C findings fail with or without it
     --no-packed-with-mfma  r06, the isolated form of the same defect (tools/ubench/pk_vs_mfma_waves2.hip, profiles/r06_packed_f32_vs_mfma.txt):
                            v_pk_{fma,mul,add}_f32 loses the LOW half of its result in lanes 48-63 while ANOTHER wave of the SIMD
                            issues MFMAs at certain distances -- nothing in the wave's own instruction stream prevents it.  Fails if
@@ -36,9 +39,10 @@ identical to source C is the normal accumulate form and is not reported.
                            the matrix pipe).  An INVENTORY, not a defect list: tools/ubench/mfma_war.hip / mfma_valu_war.hip
                            show the hardware interlocks this pattern (a rejected hypothesis for r05's run-to-run
                            differences; flow.hip has thousands of such sites and has never flickered)
-csrc/Makefile runs it on emd.s with the first three options before emd.o may be linked, and on EVERY object's assembly with
---no-packed-with-mfma --no-packed-before-mfma: determinism of those kernels is a property of the compiled code (ADVICE r05,
-include/dpf_hip.h at dpf_emd_set_matrix_path).
+csrc/Makefile runs it ONCE on every object's assembly before the object is compiled: with the three --no-packed-* rules (GATE), and
+with the object's own arguments (GATE_<object>: --ignore-overlap for every object but emd.o, which adds --require-register-c
+--no-scratch emd_mfma_ --no-packed-f32 emd_mfma_; --no-scratch PREFIX for the kernels that must keep their data in registers).
+Determinism of those kernels is a property of the compiled code (include/dpf_hip.h at dpf_emd_set_matrix_path).
 """
 import re
 import sys
@@ -123,7 +127,9 @@ def scan_packed_with_mfma(path):
 
 
 def scan(path, require_register_c=False, no_scratch=None, no_packed=None):
-    bad, kernel, total = [], None, 0
+    """(MFMA count, overlap findings, other findings): the destination-overlap findings are the ones --ignore-overlap tolerates; the
+    register-C, packed-in-kernel and scratch findings always fail"""
+    overlap, bad, kernel, total = [], [], None, 0
     for line in open(path):
         m = re.match(r"^(\S+):\s", line)
         if m and not m.group(1).startswith("."):
@@ -137,7 +143,7 @@ def scan(path, require_register_c=False, no_scratch=None, no_packed=None):
         total += 1
         dst, a, b = regs(ops[0]), regs(ops[1]), regs(ops[2])
         if overlaps(dst, a) or overlaps(dst, b):
-            bad.append((kernel, line.strip()))
+            overlap.append((kernel, line.strip()))
         elif require_register_c and regs(ops[3].split()[0] if len(ops) > 3 else "") is None:
             bad.append((kernel, line.strip() + "    ; C is not a register tuple"))
     if no_packed:
@@ -157,7 +163,7 @@ def scan(path, require_register_c=False, no_scratch=None, no_packed=None):
             if kernel and no_scratch in kernel and re.search(r"\bscratch_(load|store)", line):
                 bad.append((kernel, line.strip() + "    ; scratch in a kernel that must not spill"))
                 break
-    return total, bad
+    return total, overlap, bad
 
 
 LOADS = re.compile(r"\s*(global_load_\S+|buffer_load_\S+|scratch_load_\S+|flat_load_\S+|ds_read\S*|ds_load\S*)\s+(.*)")
@@ -214,7 +220,7 @@ def main(argv):
     nop = argv[argv.index("--no-packed-f32") + 1] if "--no-packed-f32" in argv else None
     paths = [a for i, a in enumerate(argv) if not a.startswith("--") and (i == 0 or argv[i - 1] not in ("--no-scratch", "--no-packed-f32"))]
     for p in paths:
-        total, bad = scan(p, req, nos, nop)
+        total, overlap, bad = scan(p, req, nos, nop)
         if "--war" in argv:
             war = scan_war(p)
             print("%s: %d loads into the A / B registers of an MFMA still in flight" % (p, len(war)))
@@ -239,9 +245,9 @@ def main(argv):
             for k, a, b in pairs:
                 print("   %s: %s  ->  %s" % ((k or "?")[:50], a, b))
                 rc = 1
-        print("%s: %d MFMA instructions, %d with the destination on a source's registers" % (p, total, len(bad)))
-        if "--ignore-overlap" in argv:          # (the library-wide gate: the packed-fp32 rules only)
-            continue
+        print("%s: %d MFMA instructions, %d with the destination on a source's registers" % (p, total, len(overlap)))
+        if "--ignore-overlap" not in argv:      # (the library-wide gate tolerates these, and these only)
+            bad = overlap + bad
         for k, l in bad:
             print("   %s: %s" % (k[:60], l))
             rc = 1
