@@ -142,6 +142,7 @@ SIGNATURES = {
     "dpf_swd_grad": (_i, [_i, _i, _i] + [_vp] * 10 + [_vp, _sz, _vp]),
     "dpf_knn_max_k": (_i, []),
     "dpf_knn": (_i, [_i, _i, _vp, _l, _l, _l, _i, _vp, _l, _l, _l, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "dpf_normals": (_i, [_i, _i, _i, _vp, _l, _l, _l, _vp, _i, _vp, _l, _vp, _vp, _vp, _vp, _vp]),
     "dpf_version": (ctypes.c_char_p, []),
 }
 

@@ -408,5 +408,18 @@ inline KNNForm knn_form(int k, int force) {
     return {k <= 4 ? 4 : k <= 8 ? 8 : k <= 16 ? 16 : 32};
 }
 
+// ---- point-cloud normals (normals.hip) ---------------------------------------------------------------------------------------------
+constexpr int NORMALS_MIN_K = 3;        // fewer points span no plane
+constexpr int NORMALS_MAX_K = KNN_MAX_K;    // dpf_knn's largest list: a lane keeps its k gathered points in registers (3 VGPRs each)
+constexpr int NORMALS_WG_POINTS = 64;   // one wave a workgroup, one point a lane: no LDS, no barrier, so the smallest workgroup spreads best
+constexpr int NORMALS_SWEEPS = 6;       // cyclic Jacobi sweeps of the 3 x 3 covariance: 4 reach the rounding floor, 6 are run
+// kcap: the neighbourhood capacity the kernel is instantiated for, 4 | 8 | 16 | 32 -- the smallest >= k (its gather is unrolled over
+// kcap; the outputs do not depend on it).  Unserved (kcap 0): k outside NORMALS_MIN_K..NORMALS_MAX_K.
+struct NormalsForm { int kcap; };
+inline NormalsForm normals_form(int k) {
+    if (k < NORMALS_MIN_K || k > NORMALS_MAX_K) return {0};
+    return {k <= 4 ? 4 : k <= 8 ? 8 : k <= 16 ? 16 : 32};
+}
+
 }  // namespace dispatch
 #endif  // DPF_DISPATCH_H

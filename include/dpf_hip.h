@@ -1028,6 +1028,52 @@ int dpf_knn(int B, int n, const float *query, long q_cloud_stride, long q_point_
             long c_cloud_stride, long c_point_stride, long c_axis_stride, int k, int exclude_same_index, int form, float *dist,
             int *index, int *status, dpf_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * Point-cloud normals by local PCA (csrc/normals.hip): per query point the covariance of its k listed neighbours, the eigenvalues of
+ * that 3 x 3 matrix and the unit eigenvector of the smallest one -- the surface normal of the neighbourhood -- with a defined sign.
+ * Not a port: the reference has no normals.  tests/normals_ref.py restates all of this in numpy float64.  No gradient.
+ *   Input: cloud holds B sets of m points, fp32, read in place through the three strides dpf_knn takes (counted in floats; a cloud
+ *     stride of 0 broadcasts one set).  index: (B, n, k) int32, dense -- what dpf_knn writes: row (b, i) lists the neighbourhood of
+ *     query point i of slot b.  viewpoint: fp32, 3 values per slot at viewpoint + b * viewpoint_stride (in floats; 0 broadcasts one),
+ *     or NULL for none.  Nothing is written but the outputs.
+ *   Arguments: 3 <= k <= 32.  k < 3 returns DPF_EINVAL, as do B < 0, n < 1, m < 1 and a missing cloud, index, normal, eigenvalues or
+ *     flag; k > 32 returns DPF_ENOSUP; B == 0 launches nothing.  k may exceed m (a list may repeat a point).
+ *   Outputs, all dense: normal (B, n, 3) and eigenvalues (B, n, 3, ascending) float64; cov (B, n, 6) float64 in the order xx, xy, xz,
+ *     yy, yz, zz, optional (NULL: not written); flag (B, n) int32.
+ *   Validity is per POINT: point i is flagged when any of its k indices lies outside [0, m), or any gathered coordinate is not finite
+ *     or exceeds 2^61 in magnitude.  A flagged point gets flag 1 and NaN in every floating output; a valid one flag 0; no other point
+ *     is touched.  Every index is range-checked BEFORE it is used as an address: a table full of -1 (dpf_knn's refused slot) gives a
+ *     table full of flags, never a load outside the cloud.  The call still returns 0.
+ *   Covariance, bit-defined -- every operation a separately rounded float64 operation (no contraction), on the gathered fp32
+ *     coordinates converted to float64:
+ *       centroid  c_a = (p_0,a + p_1,a + ... + p_k-1,a) / (double) k     added in ascending s starting from p_0; one IEEE division
+ *       C_ab = sum_s (p_s,a - c_a) * (p_s,b - c_b)                       each product rounded on its own; added in ascending s
+ *                                                                        starting from the s = 0 term
+ *     The two-pass form: clouds sit at offsets like 100 with 1e-3 of local spread, where sum(pp) - sum(p) sum(p) / k cancels.  No
+ *     division by k or k - 1: the scale changes no eigenvector.  Within the 2^61 bound nothing overflows: (2^62)^2 * 32 < 2^130.
+ *   Eigen-decomposition: cyclic Jacobi on the symmetric matrix, a FIXED 6 sweeps over the pairs (0, 1), (0, 2), (1, 2), no convergence
+ *     test.  A rotation is skipped where its off-diagonal entry a_pq is exactly 0; else theta = (a_qq - a_pp) / (2 a_pq),
+ *     t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)) with sgn(0) = +1, c = 1 / sqrt(t^2 + 1), s = t c; a_pp -= t a_pq, a_qq += t a_pq,
+ *     a_pq = 0; with r the third index (a_rp, a_rq) <- (c a_rp - s a_rq, s a_rp + c a_rq), and the columns p and q of the accumulated
+ *     rotations (initially the identity) turn the same way.  4 sweeps reach the rounding floor on every kind of neighbourhood
+ *     measured; the eigenvalues and the vector are accurate to a few units of 2^-52 * the largest eigenvalue, they are
+ *     not bit-defined against another implementation.
+ *   Which vector: the three diagonal entries are sorted ascending by the stable three-element compare network (0, 1), (1, 2), (0, 1),
+ *     swapping only where the left is strictly greater -- the lower column goes first among equals.  The normal is the column of the
+ *     smallest, divided once by its norm sqrt((x^2 + y^2) + z^2).
+ *   Sign, bit-defined given the vector: canonically the component of largest magnitude is positive, the lowest axis among equal
+ *     magnitudes.  With a viewpoint w whose three coordinates are finite, t = ((n_x (w_x - c_x)) + n_y (w_y - c_y)) + n_z (w_z - c_z)
+ *     in float64 against the neighbourhood's centroid, every product rounded on its own: t < 0 flips the canonical normal, t == 0
+ *     keeps it.  A viewpoint with a non-finite coordinate counts as none for its slot.
+ *   Determinism: every output of point i is bit-identical from run to run and depends on its own k gathered points and its slot's
+ *     viewpoint alone -- not on B, n, the strides or the launch shape.
+ *   One lane per point, one wave per workgroup, one launch (cut by dispatch::chunk_grid past 32768 slots or 2^22 workgroups a slot),
+ *     the caller's stream, no synchronisation, no LDS, no workspace, no atomics, no memset nodes.  Every loop runs over k, over 3 or
+ *     over the sweep count: no input makes a launch spin. */
+int dpf_normals(int B, int n, int m, const float *cloud, long cloud_stride, long point_stride, long axis_stride, const int *index,
+                int k, const float *viewpoint, long viewpoint_stride, double *normal, double *eigenvalues, double *cov, int *flag,
+                dpf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
