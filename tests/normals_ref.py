@@ -118,15 +118,14 @@ def canonical(vec):
 
 
 def orient(vec, centroid, viewpoint):
-    """vec (N, 3) canonical, centroid (N, 3), viewpoint (3,) fp32 or None -> the oriented normals"""
+    """vec (N, 3) canonical, centroid (N, 3), viewpoint (3,) fp32, one for all, or (N, 3), one a row, or None -> the oriented normals"""
     if viewpoint is None:
         return vec
     w = np.asarray(viewpoint, dtype=np.float32).astype(np.float64)
-    if not np.isfinite(w).all():
-        return vec
     with np.errstate(all="ignore"):
-        t = (vec[:, 0] * (w[0] - centroid[:, 0]) + vec[:, 1] * (w[1] - centroid[:, 1])) + vec[:, 2] * (w[2] - centroid[:, 2])
-    return np.where((t < 0.0)[:, None], -vec, vec)
+        t = (vec[:, 0] * (w[..., 0] - centroid[:, 0]) + vec[:, 1] * (w[..., 1] - centroid[:, 1])) + vec[:, 2] * (w[..., 2] - centroid[:, 2])
+    flip = np.isfinite(w).all(-1) & (t < 0.0)                                                # (a non-finite viewpoint is no viewpoint)
+    return np.where(flip[:, None], -vec, vec)
 
 
 def eigen(cov, sweeps=SWEEPS):
@@ -200,10 +199,12 @@ def measures(cov, vec, lam):
 
 # ---- the neighbourhoods and clouds of the tests, from a seed -------------------------------------------------------------------------
 KINDS = ("gauss", "squashed", "planar", "collinear", "offset", "lattice", "equal", "scaled")
+SMALL_KINDS = ("tiny", "denormal")                  # gauss x 2^-70: the covariance near 2^-140; x 2^-135: the fp32 coordinates subnormal
+SMALL_SCALE = {"tiny": 2.0 ** -70, "denormal": 2.0 ** -135}
 
 
 def neighbourhoods(kind, count, k, seed):
-    """(count, k, 3) fp32: the eight kinds the sweep count was chosen on"""
+    """(count, k, 3) fp32: the eight kinds the sweep count was chosen on, and the two small scales"""
     rng = np.random.default_rng(seed)
     g = rng.standard_normal((count, k, 3))
     if kind == "gauss":
@@ -223,6 +224,8 @@ def neighbourhoods(kind, count, k, seed):
         p = np.repeat(g[:, :1], k, axis=1)
     elif kind == "scaled":
         p = 1e18 * g
+    elif kind in SMALL_KINDS:
+        p = SMALL_SCALE[kind] * g
     else:
         raise ValueError(kind)
     return p.astype(np.float32)
@@ -230,7 +233,8 @@ def neighbourhoods(kind, count, k, seed):
 
 def make_cloud(kind, n, seed):
     """(n, 3) fp32 clouds for the device tests.  scaled: 1e18 g with g cut at +-2.25, so that every coordinate stays inside the 2^61 =
-    2.3e18 that dpf_knn and dpf_normals serve (a plain 1e18 g would have a slot refused at its first 2.4-sigma coordinate)"""
+    2.3e18 that dpf_knn and dpf_normals serve (a plain 1e18 g would have a slot refused at its first 2.4-sigma coordinate); tiny,
+    denormal: g x 2^-70 and g x 2^-135 (SMALL_SCALE) -- the second's fp32 coordinates are subnormal"""
     rng = np.random.default_rng(seed)
     g = rng.standard_normal((n, 3))
     if kind == "gauss":
@@ -245,6 +249,8 @@ def make_cloud(kind, n, seed):
         p = g * np.array([1.0, 1.0, 1e-3])
     elif kind == "lattice":
         p = rng.integers(-3, 4, size=(n, 3)).astype(np.float64)
+    elif kind in SMALL_KINDS:
+        p = SMALL_SCALE[kind] * g
     else:
         raise ValueError(kind)
     return p.astype(np.float32)

@@ -102,3 +102,115 @@ def test_spacing_and_gradient_formulas():
             num = (f(up, c) - f(dn, c)) / (2 * h) if arr is q else (f(q, up) - f(q, dn)) / (2 * h)
             assert abs(num - got[at]) < 1e-6
     assert (aq >= np.abs(gq)).all() and (ac >= np.abs(gc)).all()
+
+
+# ---- the inputs of tests/test_gpu_knn_edges.py: that they reach what they are for, and that a wrong kernel would show on them --------
+def test_candidate_orders_load_the_queue_as_claimed_at_every_capacity():
+    """hot lanes improve on >= 0.9 m candidates, ordinary and cold ones on <= 0.25 m, at each list capacity (the GPU test asserts
+    the same at the capacity it runs)"""
+    m, n = 1025, 320
+    query, cloud, hot = R.order_batch(m, n)
+    d0 = R.dist2(R.ORIGIN, cloud[0])[0]
+    assert (np.diff(d0) < 0).all() and np.array_equal(cloud[1], cloud[0][::-1])              # strictly descending, and its reverse
+    assert (np.sqrt((query[0].astype(np.float64) ** 2).sum(1)) <= 1e-3).all()
+    assert hot.sum(1).tolist() == [n, 0, n // 2, n // 2, 1] and hot[4, 101]
+    shuffled = R.dist2(query[0], R.make_cloud("gauss", m, 11))
+    for cap in (4, 8, 16, 32):
+        count = np.stack([R.improvements(R.dist2(query[b], cloud[b]), cap) for b in range(5)])
+        print("capacity %2d: hot minimum %d, ordinary maximum %d, cold maximum %d, shuffled maximum %d of %d"
+              % (cap, count[hot].min(), count[2:][~hot[2:]].max(), count[1].max(), R.improvements(shuffled, cap).max(), m))
+        assert count[hot].min() >= 0.9 * m and count[~hot].max() <= 0.25 * m, cap
+        assert (count[1] == cap).all()                                                      # ascending: the first `cap` and nothing after
+
+
+def test_improvements_counts_insertions_under_an_exact_threshold():
+    assert R.improvements(np.array([5.0, 4.0, 3.0, 2.0, 1.0]), 2) == 5
+    assert R.improvements(np.array([1.0, 2.0, 3.0, 4.0, 5.0]), 2) == 2
+    assert R.improvements(np.array([3.0, 3.0, 3.0, 3.0]), 2) == 2                            # strict: an equal distance is no improvement
+    assert R.improvements(np.array([3.0, np.inf, 1.0, 2.0, 0.5]), 2) == 4                    # (+inf, the excluded one, never counts)
+    assert R.improvements(np.array([[4.0, 3.0, 5.0, 1.0], [1.0, 1.0, 0.0, 0.0]]), 1).tolist() == [3, 2]
+
+
+def test_shells_are_integer_distances_in_long_descending_runs():
+    m = 1025
+    cloud = R.shells(m)
+    assert cloud.shape == (m, 3) and (cloud == np.round(cloud)).all() and np.abs(cloud).max() <= 6
+    assert len({tuple(p) for p in cloud.tolist()}) == m
+    d = R.dist2(R.ORIGIN, cloud)[0]
+    assert (np.diff(d) <= 0).all() and d[-1] == 0 and (d == np.round(d)).all()
+    assert round(float((np.diff(d) == 0).mean()), 2) == 0.97 and R.longest_run(d) == 72
+    ends = np.concatenate([np.flatnonzero(np.diff(d)) + 1, [m]])
+    for lo, hi in zip(np.concatenate([[0], ends[:-1]]), ends):
+        run = cloud[lo:hi]                                                                  # inside a run: the lattice's own (x fastest) order
+        key = (run[:, 2] * 13 + run[:, 1]) * 13 + run[:, 0]
+        assert (np.diff(key) > 0).all()
+    query = np.concatenate([R.ORIGIN, cloud[:7]])
+    for k in (1, 5, 32):
+        dist, index, _ = R.knn(query, cloud, k)
+        wd, wi = R.brute_force(query, cloud, k)
+        assert np.array_equal(index, wi) and np.array_equal(dist.astype(np.float64), wd)
+    dist, index, _ = R.knn(cloud[:8], cloud, 32, True)
+    wd, wi = R.brute_force(cloud[:8], cloud, 32, True)
+    assert np.array_equal(index, wi) and np.array_equal(dist.astype(np.float64), wd)
+
+
+def test_descending_and_huge_agree_with_float64_where_it_separates_the_neighbours():
+    """(not `tiny`: float64 does not tie where fp32's subnormals do, so there is nothing to compare)"""
+    query, cloud, _ = R.order_batch()
+    q = np.concatenate([query[0][:4], query[2][1:4]])                                       # hot ones and ordinary ones
+    dist, index, _ = R.knn(q, cloud[0], 9)
+    wd, wi = R.brute_force(q, cloud[0], 10)
+    clear = (np.diff(wd, axis=1) > 2.0 ** -20 * wd[:, 1:]).all(1)                            # fp32 error of a distance: a few 2^-24 of it
+    assert clear.sum() >= 5 and np.array_equal(index[clear], wi[clear][:, :9])
+    assert (np.abs(dist - wd[:, :9]) <= 2.0 ** -21 * wd[:, :9]).all()
+    huge = R.make_range_cloud("huge", 300, 5)
+    dist, index, status = R.knn(huge[:6], huge, 9, True)
+    wd, wi = R.brute_force(huge[:6], huge, 10, True)
+    clear = (np.diff(wd, axis=1) > 2.0 ** -20 * wd[:, 1:]).all(1)
+    assert status == 0 and clear.sum() >= 4 and np.array_equal(index[clear], wi[clear][:, :9])
+    assert (np.abs(dist - wd[:, :9]) <= 2.0 ** -21 * wd[:, :9]).all()
+
+
+def test_the_ends_of_the_range_are_what_they_are_for():
+    tiny, huge, wide = (R.make_range_cloud(kd, 300, 5) for kd in ("tiny", "huge", "wide"))
+    assert np.array_equal(tiny, R.make_cloud("gauss", 300, 5) * np.float32(2.0 ** -70))
+    assert (tiny.astype(np.float64) * 2.0 ** 70 == R.make_cloud("gauss", 300, 5)).all()      # (the scaling is exact)
+    d = R.dist2(tiny, tiny)
+    assert R.subnormal_share(d) > 0.99 and (d[~((d > 0) & (d < R.SUBNORMAL))] == 0).all()
+    assert (np.diff(R.knn(tiny, tiny, 32, True)[0], axis=1) == 0).mean() > 0.01
+    assert np.abs(huge).max() == R.LIMIT and (huge == R.LIMIT).any() and (huge == -R.LIMIT).any()
+    dist, _, status = R.knn(huge, huge, 299, True)
+    assert status == 0 and np.isfinite(dist).all() and dist.max() == np.float32(3 * 2.0 ** 124)
+    assert np.abs(wide).max() > 2.0 ** 55 and np.abs(wide).min() < 2.0 ** -55 and R.knn(wide, wide, 32)[2] == 0
+
+
+def same(a, b):
+    return all(np.array_equal(np.ascontiguousarray(x).view(np.uint8), np.ascontiguousarray(y).view(np.uint8)) for x, y in zip(a, b))
+
+
+def test_a_kernel_with_the_wrong_tie_rule_would_show():
+    """highest index first among equals: on the lattice of the older tests, and on `shells` and `tiny`"""
+    lat, sh, tiny = R.make_cloud("lattice", 300, 3), R.shells(1025), R.make_range_cloud("tiny", 300, 5)
+    for cloud, query in ((lat, lat), (sh, np.concatenate([R.ORIGIN, sh[:9]])), (tiny, tiny)):
+        for exclude in (False, True):
+            assert not same(R.knn_highest_index_first(query, cloud, 5, exclude)[:2], R.knn(query, cloud, 5, exclude)[:2])
+    g = R.make_cloud("gauss", 300, 3)                                                       # (and it is the tie rule alone that differs)
+    assert same(R.knn_highest_index_first(g, g, 5, True), R.knn(g, g, 5, True))
+
+
+def test_a_kernel_that_flushes_subnormals_would_show_on_tiny_and_nowhere_else():
+    tiny, g = R.make_range_cloud("tiny", 300, 5), R.make_cloud("gauss", 300, 5)
+    for exclude in (False, True):
+        assert not same(R.knn_flushed(tiny, tiny, 9, exclude)[:2], R.knn(tiny, tiny, 9, exclude)[:2])
+        assert same(R.knn_flushed(g, g, 9, exclude), R.knn(g, g, 9, exclude))
+    assert (R.knn_flushed(tiny, tiny, 9)[0] == 0).all()
+
+
+def test_a_status_written_at_the_slot_within_its_launch_would_show():
+    query, cloud = R.launch_batch(B=32769, n=1, m=2)                                        # (the statuses need no more)
+    q, c = R.poison(query, cloud)
+    status = R.knn_batch(q, c, 1)[2]
+    assert np.flatnonzero(status).tolist() == [32767, 32768]
+    wrong = R.status_at_slot_mod(status)
+    assert np.flatnonzero(wrong).tolist() == [0, 32767] and not np.array_equal(wrong, status)
+    assert np.array_equal(R.status_at_slot_mod(status[:32768]), status[:32768])              # (one launch: nothing to tell apart)

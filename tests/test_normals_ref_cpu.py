@@ -45,6 +45,42 @@ def test_the_restatement_holds_the_four_bounds_against_eigh(k):
             assert measured == COUNT, kind                                                  # (the angle bound is not vacuous there)
 
 
+@pytest.mark.parametrize("k", KS)
+def test_the_restatement_holds_the_four_bounds_at_small_scales(k):
+    """gauss x 2^-70 (covariances near 2^-140) and gauss x 2^-135, whose fp32 coordinates are themselves subnormal (covariances near
+    2^-270): float64 is nowhere near its own underflow at 2^-1022, and numpy.linalg.eigh keeps its accuracy there -- measured, the
+    figures equal those of the same covariances multiplied by 2^140 and 2^270 -- so the bounds are held against eigh of the
+    covariance as it is, and against the scaled one as well."""
+    for kind in R.SMALL_KINDS:
+        pts = R.neighbourhoods(kind, COUNT, k, 1000 * k + 50 + R.SMALL_KINDS.index(kind))
+        if kind == "denormal":
+            assert ((np.abs(pts) < 2.0 ** -126) & (pts != 0)).mean() > 0.99                  # subnormal, and not flushed away
+        _, cov = R.covariance(pts)
+        vec, lam = R.eigen(cov)
+        assert np.isfinite(vec).all() and np.isfinite(lam).all() and (np.diff(lam, axis=1) >= 0).all(), kind
+        assert 0 < np.abs(cov).max() < 2.0 ** (-130 if kind == "tiny" else -255)
+        up = 2.0 ** (140 if kind == "tiny" else 270)
+        for what, scale in (("as it is", 1.0), ("scaled up", up)):
+            res, norm, ev, angle, measured = R.measures(cov * scale, vec, lam * scale)
+            print("k %2d %-8s %-9s residual %6.2f eps, | |v| - 1 | %5.2f eps, eigenvalues %6.2f eps, angle %6.2f eps on %d of %d"
+                  % (k, kind, what, res / EPS, norm / EPS, ev / EPS, angle / EPS, measured, COUNT))
+            assert res <= BOUND and norm <= BOUND and ev <= BOUND and angle <= BOUND, (kind, what, res, norm, ev, angle)
+            assert k == 3 or measured == COUNT, kind
+        assert (R.canonical_flip(vec) == 0).all(), kind
+        gauss = R.neighbourhoods("gauss", COUNT, k, 1000 * k + 50 + R.SMALL_KINDS.index(kind))
+        if kind == "tiny":                                                                  # an exact power of two: the unit-scale cloud's digits
+            assert np.array_equal(pts.astype(np.float64) * 2.0 ** 70, gauss.astype(np.float64))
+
+
+def test_a_viewpoint_per_row():
+    n = np.array([[0.0, 0.0, 1.0]] * 4)
+    c = np.array([[1.0, 2.0, 0.5]] * 4)
+    w = np.array([[0, 0, 3], [0, 0, -3], [np.nan, 0, -3], [7, -9, 0.5]], dtype=np.float32)
+    assert R.orient(n, c, w)[:, 2].tolist() == [1.0, -1.0, 1.0, 1.0]
+    for row in range(4):
+        assert np.array_equal(R.orient(n, c, w)[row], R.orient(n[row:row + 1], c[row:row + 1], w[row])[0])
+
+
 def test_three_sweeps_are_not_enough_and_four_equal_six():
     """the sweep count's margin: 3 sweeps leave a residual far above the bound somewhere, 4 give what 6 give"""
     worst3 = 0.0
