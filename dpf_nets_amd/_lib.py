@@ -143,7 +143,10 @@ SIGNATURES = {
     "dpf_knn_max_k": (_i, []),
     "dpf_knn": (_i, [_i, _i, _vp, _l, _l, _l, _i, _vp, _l, _l, _l, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "dpf_normals": (_i, [_i, _i, _i, _vp, _l, _l, _l, _vp, _i, _vp, _l, _vp, _vp, _vp, _vp, _vp]),
-    "dpf_version": (ctypes.c_char_p, []),
+    "dpf_align_workspace_bytes": (_sz, [_i, _i]),
+    "dpf_rigid_fit": (_i, [_i, _i, _vp, _l, _l, _l, _vp, _l, _l, _l, _vp, _i] + [_vp] * 6 + [_vp, _sz, _vp]),
+    "dpf_icp": (_i, [_i, _i, _vp, _l, _l, _l, _i, _vp, _l, _l, _l, _i, _f, _i] + [_vp] * 11 + [_vp, _sz, _vp]),
+    "dpf_version":(ctypes.c_char_p, []),
 }
 
 PREC = {"bf16": 1, "bf16x3": 2, "bf16x6": 3, "f16x3": 4}

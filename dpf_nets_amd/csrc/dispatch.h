@@ -421,5 +421,20 @@ inline NormalsForm normals_form(int k) {
     return {k <= 4 ? 4 : k <= 8 ? 8 : k <= 16 ? 16 : 32};
 }
 
+// ---- rigid alignment (align.hip) ---------------------------------------------------------------------------------------------------
+constexpr int ALIGN_WG_POINTS = 256;    // source points of a workgroup: 4 waves, one point per lane -- and the block of the sums' tree
+constexpr int ALIGN_TILE = 256;         // target points per LDS tile (3 KB, structure of arrays), as KNN_TILE
+constexpr int ALIGN_SUMS = 18;          // float64 quantities per slot: W, S_p (3), S_q (3), S_pq (9), S_pp, S_d
+constexpr int ALIGN_SWEEPS = 7;         // cyclic Jacobi sweeps of Horn's 4 x 4 matrix: 5 reach the rounding floor, 7 are run
+constexpr int ALIGN_MIN_INLIERS = 3;    // fewer matched points fix no rotation
+// blocks: workgroups of a slot's match (or accumulate) launch = block partials a slot's solve wave adds up, in ascending order;
+// launches: kernels a call puts on the stream -- a match and a solve per iteration and one more pair for the returned transform
+// (dpf_rigid_fit: iters = 0).  Unserved (blocks 0): n < 1 or iters < 0.
+struct AlignForm { long blocks; long launches; };
+inline AlignForm align_form(int n, int iters) {
+    if (n < 1 || iters < 0) return {0, 0};
+    return {ceil_div(n, ALIGN_WG_POINTS), 2 * ((long)iters + 1)};
+}
+
 }  // namespace dispatch
 #endif  // DPF_DISPATCH_H

@@ -1074,6 +1074,86 @@ int dpf_normals(int B, int n, int m, const float *cloud, long cloud_stride, long
                 int k, const float *viewpoint, long viewpoint_stride, double *normal, double *eigenvalues, double *cov, int *flag,
                 dpf_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * Rigid alignment (csrc/align.hip): the weighted Procrustes fit of given correspondences (dpf_rigid_fit) and trimmed point-to-point
+ * ICP (dpf_icp) -- what makes the metrics above usable on clouds that do not arrive in one frame.  Not a port: the reference has no
+ * registration.  tests/align_ref.py restates all of this in numpy.  No gradient.
+ *   Both minimise sum_i w_i |s R p_i + t - q_i|^2 over a proper rotation R (det = +1), a translation t and a scale s (s = 1 unless
+ *     with_scale != 0).  A transform is 13 float64 values: R row-major (9), t (3), s.
+ *   Input: src holds B sets of n points and dst B sets of m points (dpf_rigid_fit: n), fp32, each read in place through the three
+ *     strides dpf_knn takes (counted in floats; a cloud stride of 0 broadcasts one set).  Neither is written.
+ *     dpf_rigid_fit: point i of src belongs to point i of dst; weights (B, n) fp32 dense, optional (NULL: every weight 1).
+ *     dpf_icp: init (B, 13) float64 dense, optional (NULL: the identity for every slot); max_dist2 the squared trim distance
+ *     (<= 0, +inf or NaN: no trim).
+ *   dpf_icp, iteration k = 0 .. iters - 1: (1) MATCH every source point, under the current transform, to its nearest target point;
+ *     (2) SOLVE for the absolute transform from the ORIGINAL source points to their matches -- increments are never composed, so
+ *     nothing drifts.  After the last solve one more match runs under the returned transform, and a last reduction of it: index,
+ *     dist, sums and the last rmse and inliers belong to what is returned.  2 (iters + 1) launches (dpf_rigid_fit: 2).
+ *   Match, bit-defined:
+ *     y_a = fp32( ((R_a0 p_0 + R_a1 p_1) + R_a2 p_2) * s + t_a )   float64 on the fp32 coordinates converted to float64, every
+ *                                                                    product and sum rounded on its own, ONE rounding to fp32
+ *     A y with a component that is not finite or exceeds 2^61 in magnitude has no match: index -1, dist +inf, weight 0.
+ *     d(i, j) = (dx*dx + dy*dy) + dz*dz with dx = c_j.x - y.x, fp32, no contraction: dpf_nndistance's bits.  The match is the smallest
+ *     key (d, j), the LOWEST index among equal distances.  With a trim a match with d > max_dist2 becomes index -1 and weight 0
+ *     (dist keeps d).  Matched points have weight 1.  changed = the number of points whose index differs from the one the iteration
+ *     before wrote (an inlier turning outlier or back is a change: the outlier is -1); iteration 0 counts every point.
+ *   Sums, bit-defined: eighteen float64 quantities per slot over the pivoted points p' = p - a, q' = q - c in float64, a = source
+ *     point 0 of the slot and c = target point 0 (dpf_rigid_fit: point 0 of either set), in this order:
+ *       [0] W = sum w   [1..3] S_p = sum (w p'_a)   [4..6] S_q = sum (w q'_a)   [7 + 3a + b] S_pq = sum ((w p'_a) q'_b)
+ *       [16] S_pp = sum w ((p'_0^2 + p'_1^2) + p'_2^2)   [17] dpf_icp: S_d = sum w (double) d;  dpf_rigid_fit: S_qq, [16]'s form on q'
+ *     every product rounded on its own; a point without a match contributes +0.0 to all eighteen.  One pass over pivoted points: a
+ *     cloud at offset 100 with 1e-3 of spread keeps its digits.  ORDER: a block is 256 consecutive points; its sum is the pairwise
+ *     tree  for stride = 128, 64, ..., 1: x[i] += x[i + stride]  over the block's terms (+0.0 past n); the block sums are added in
+ *     ascending block order starting from block 0's.  The inlier count (w > 0) and changed are integer sums.
+ *   Solve, float64, every operation rounded on its own: with W > 0,
+ *       M_ab = S_pq_ab - (S_p_a S_q_b) / W      v = S_pp - ((S_p0^2 + S_p1^2) + S_p2^2) / W
+ *     Horn's closed form: the symmetric 4 x 4 matrix
+ *       N = [[(Mxx+Myy)+Mzz, Myz-Mzy,        Mzx-Mxz,         Mxy-Myx        ],
+ *            [ .             (Mxx-Myy)-Mzz,  Mxy+Myx,         Mzx+Mxz        ],
+ *            [ .             .               (-Mxx+Myy)-Mzz,  Myz+Mzy        ],
+ *            [ .             .               .                (-Mxx-Myy)+Mzz ]]
+ *     is diagonalised by cyclic Jacobi with dpf_normals' rotation over the pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), a FIXED 7 sweeps,
+ *     no convergence test (5 reach the rounding floor: DESIGN 4.5i).  The column of the largest diagonal entry (the lowest column
+ *     among equals), divided once by its norm sqrt(((q0^2 + q1^2) + q2^2) + q3^2), its sign fixed so that its component of largest
+ *     magnitude is positive (the lowest among equals), is the unit quaternion (q0; q1, q2, q3) = (w; x, y, z) of
+ *       R = [[((ww+xx)-yy)-zz, 2(xy-wz),         2(xz+wy)       ],
+ *            [2(xy+wz),        ((ww-xx)+yy)-zz,  2(yz-wx)       ],
+ *            [2(xz-wy),        2(yz+wx),         ((ww-xx)-yy)+zz]]
+ *     so det R = +1 always: there is no reflection to fix.  s = (sum_ab R_ab M_ba) / v with with_scale, else 1;
+ *     t_a = (c_a + S_q_a / W) - s * ((R_a0 g_0 + R_a1 g_1) + R_a2 g_2) with g = a + S_p / W.  R, t and s are accurate to
+ *     ALIGN_BOUND (tests/align_ref.py) relative to their scales; they are not bit-defined against another implementation, but they
+ *     are bit-identical from run to run.
+ *   Degenerate: fewer than 3 inliers, W = 0, v <= 0 under with_scale, or a non-finite entry in the result.  The slot keeps the
+ *     transform it had (the init, or the identity), gets status DPF_ALIGN_DEGENERATE and stops iterating.
+ *   Refused: a slot with a coordinate of src or dst, an entry of its init or a weight that is not finite or exceeds 2^30 in magnitude,
+ *     or a negative weight (every product then stays below 2^61 and every sum finite).  It gets NaN in R, t, s, rmse, sums and
+ *     dist, index -1, inliers 0, iterations 0 and status DPF_ALIGN_REFUSED; no other slot is touched.
+ *   Convergence: when a match after the first finds changed == 0 the next solve would return the same bits; the slot is done and
+ *     iterations = the number of solves that gave its transform.  Later launches leave a done slot's outputs in place; the rmse and
+ *     inliers entries after it repeat the last value.  A slot that never converges has iterations = iters.
+ *   Outputs, all dense: R (B, 3, 3), t (B, 3), s (B) float64; status (B) int32: 0, DPF_ALIGN_DEGENERATE or DPF_ALIGN_REFUSED; sums
+ *     (B, 18) float64, optional (NULL: not written).  dpf_icp: index (B, n) int32 and dist (B, n) fp32 of the final match; rmse
+ *     (B, iters + 1) float64 = sqrt(S_d / W) per match (NaN where W = 0); inliers (B, iters + 1) int32; iterations (B) int32.
+ *     dpf_rigid_fit: rmse (B) = sqrt(e / W) from the closed form e = max(0, ((s s) v + v_q) - (2 s) sum_ab R_ab M_ba), v_q as v from
+ *     S_qq and S_q: it cancels, so it is good to about 2^-26 of the clouds' spread (NaN for a degenerate slot).
+ *   Arguments: B < 0, n < 1, m < 1, iters < 0, a missing pointer other than weights, init or sums, a workspace that is not 8-byte
+ *     aligned or smaller than dpf_align_workspace_bytes(B, n) return DPF_EINVAL; B == 0 launches nothing.  The workspace is
+ *     caller-owned and need not be cleared: iteration 0 takes "everything changed" from an argument.
+ *   Determinism: every output is bit-identical from run to run and depends on the slot's own inputs alone -- not on B, the strides
+ *     or the launch shape.  The caller's stream, no synchronisation, no memset nodes, no atomics; launches are cut by
+ *     dispatch::chunk_grid.  Every loop runs over n, m, the block count, the sweep count or six pairs: no input makes a launch spin. */
+#define DPF_ALIGN_DEGENERATE 1
+#define DPF_ALIGN_REFUSED (-1)
+size_t dpf_align_workspace_bytes(int B, int n);
+int dpf_rigid_fit(int B, int n, const float *src, long s_cloud_stride, long s_point_stride, long s_axis_stride, const float *dst,
+                  long d_cloud_stride, long d_point_stride, long d_axis_stride, const float *weights, int with_scale, double *R,
+                  double *t, double *s, double *rmse, double *sums, int *status, void *workspace, size_t workspace_bytes,
+                  dpf_stream_t stream);
+int dpf_icp(int B, int n, const float *src, long s_cloud_stride, long s_point_stride, long s_axis_stride, int m, const float *dst,
+            long d_cloud_stride, long d_point_stride, long d_axis_stride, int iters, float max_dist2, int with_scale,
+            const double *init, double *R, double *t, double *s, int *index, float *dist, double *rmse, int *inliers,
+            int *iterations, double *sums, int *status, void *workspace, size_t workspace_bytes, dpf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
