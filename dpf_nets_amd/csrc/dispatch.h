@@ -436,5 +436,27 @@ inline AlignForm align_form(int n, int iters) {
     return {ceil_div(n, ALIGN_WG_POINTS), 2 * ((long)iters + 1)};
 }
 
+// ---- density-aware Chamfer distance (dcd.hip) ----------------------------------------------------------------------------------------
+constexpr int DCD_BLOCK = 256;            // queries of a block of the sums' tree (ALIGN_WG_POINTS: the same tree)
+constexpr int DCD_LDS_THREADS = 1024;     // the one-workgroup form: four blocks of the tree a step
+constexpr int DCD_LDS_TARGETS = 32768;    // its histogram: 4 bytes a target, 128 KB of the workgroup's 160, 8 KB beside it for the tree
+// Lds: one workgroup a cloud, the counts an int32 histogram in LDS, ONE launch; Workspace: the counts in the workspace, four launches
+// (zero, count, terms over (cloud, block), one finishing wave a cloud).  Both return the same bits.  blocks1 / blocks2: the blocks of
+// side 1's n and side 2's m queries = the float64 partials a cloud's finishing wave adds up, in ascending order.
+// force: 0 by size, 1 Lds, 2 Workspace; Unserved: B < 0, n < 1, m < 1, an unknown form, Lds forced past DCD_LDS_TARGETS.
+// By size: Lds wherever both target sets fit its histogram (profiles/dcd_forms.txt, us per call, Lds | Workspace):
+//   32 x 2048 x 2048: 28.5 | 35.0     50 x 2500 x 2500: 29.4 | 36.8     1 x 32768 x 32768: 114.0 | 82.6
+// One launch wins at the evaluation shapes.  One cloud at the cap is the other way round (one workgroup walks 65536 queries while
+// the chip idles); that is one measured point, not a threshold, so by size stays Lds there and a caller with such a shape asks for 2.
+enum class DCDKernel { Lds, Workspace, Unserved };
+struct DCDForm { DCDKernel kernel; long blocks1, blocks2; int launches; };
+inline DCDForm dcd_form(int B, int n, int m, int force) {
+    if (B < 0 || n < 1 || m < 1 || force < 0 || force > 2) return {DCDKernel::Unserved, 0, 0, 0};
+    const bool fits = n <= DCD_LDS_TARGETS && m <= DCD_LDS_TARGETS;
+    if (force == 1 && !fits) return {DCDKernel::Unserved, 0, 0, 0};
+    const bool lds = force == 1 || (force == 0 && fits);
+    return {lds ? DCDKernel::Lds : DCDKernel::Workspace, ceil_div(n, DCD_BLOCK), ceil_div(m, DCD_BLOCK), lds ? 1 : 4};
+}
+
 }  // namespace dispatch
 #endif  // DPF_DISPATCH_H

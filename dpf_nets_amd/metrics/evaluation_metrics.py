@@ -138,7 +138,7 @@ def _reduce_to(clouds, n_points, name):
         return farthest_point_sample(clouds.float(), n_points)
 
 
-def compute_all_metrics(sample_pcs, ref_pcs, batch_size, accelerated_cd=False, emd="approx", n_points=None, swd=None):
+def compute_all_metrics(sample_pcs, ref_pcs, batch_size, accelerated_cd=False, emd="approx", n_points=None, swd=None, dcd=None):
     """The generation metrics of the reference (:172-200): MMD and COV (lgan_mmd_cov) from the (sample, reference) matrices
     and 1-NN accuracy (knn, k = 1) from those plus the (reference, reference) and (sample, sample) matrices, for Chamfer and
     approximate EMD.  Keys "lgan_mmd-CD", "lgan_cov-CD", "lgan_mmd_smp-CD", the same for EMD, "1-NN-CD-acc_t",
@@ -153,9 +153,14 @@ def compute_all_metrics(sample_pcs, ref_pcs, batch_size, accelerated_cd=False, e
     ValueError if it exceeds either set's cloud size.
     swd: None -- the keys and values above, nothing else; an integer L -- also "lgan_mmd-SWD", "lgan_cov-SWD", "lgan_mmd_smp-SWD"
     and "1-NN-SWD-acc_t" / "-acc_f" / "-acc" from three pairwise_SWD matrices (metrics/sliced.py: the sliced 2-Wasserstein distance
-    with L directions of seed 0), in the same orientation, computed after n_points has been applied."""
+    with L directions of seed 0), in the same orientation, computed after n_points has been applied.
+    dcd: None -- nothing more; a positive alpha -- also "lgan_mmd-DCD", "lgan_cov-DCD", "lgan_mmd_smp-DCD" and "1-NN-DCD-acc_t" /
+    "-acc_f" / "-acc" from three pairwise_DCD matrices (metrics/dcd.py: the density-aware Chamfer distance at that alpha, n_lambda
+    1), in the same orientation, computed after n_points has been applied."""
     if swd is not None and (not isinstance(swd, int) or isinstance(swd, bool) or swd < 1):
         raise ValueError("swd must be a positive number of directions or None, got %r" % (swd,))
+    if dcd is not None and (isinstance(dcd, bool) or not isinstance(dcd, (int, float)) or not (0 < dcd < float("inf"))):
+        raise ValueError("dcd must be a positive finite alpha or None, got %r" % (dcd,))
     if n_points is not None:
         sample_pcs, ref_pcs = _reduce_to(sample_pcs, n_points, "sample_pcs"), _reduce_to(ref_pcs, n_points, "ref_pcs")
     results = {}
@@ -172,6 +177,12 @@ def compute_all_metrics(sample_pcs, ref_pcs, batch_size, accelerated_cd=False, e
                             for a, b in ((ref_pcs, sample_pcs), (ref_pcs, ref_pcs), (sample_pcs, sample_pcs)))
         results.update({"%s-SWD" % k: v for k, v in lgan_mmd_cov(M_rs.t()).items()})
         results.update({"1-NN-SWD-%s" % k: v for k, v in knn(M_rr, M_rs, M_ss, 1, sqrt=False).items() if 'acc' in k})
+    if dcd is not None:
+        from .dcd import pairwise_DCD
+        M_rs, M_rr, M_ss = (pairwise_DCD(a.float(), b.float(), batch_size, alpha=float(dcd))
+                            for a, b in ((ref_pcs, sample_pcs), (ref_pcs, ref_pcs), (sample_pcs, sample_pcs)))
+        results.update({"%s-DCD" % k: v for k, v in lgan_mmd_cov(M_rs.t()).items()})
+        results.update({"1-NN-DCD-%s" % k: v for k, v in knn(M_rr, M_rs, M_ss, 1, sqrt=False).items() if 'acc' in k})
     return results
 
 

@@ -1154,6 +1154,43 @@ int dpf_icp(int B, int n, const float *src, long s_cloud_stride, long s_point_st
             const double *init, double *R, double *t, double *s, int *index, float *dist, double *rmse, int *inliers,
             int *iterations, double *sums, int *status, void *workspace, size_t workspace_bytes, dpf_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * Density-aware Chamfer distance (csrc/dcd.hip): DCD of Wu et al., "Balanced Chamfer Distance as a Comprehensive Metric for Point
+ * Cloud Completion" (NeurIPS 2021), the published calc_dcd, from ONE nn_distance result per cloud: the counts, the loss and the
+ * coefficients of its gradient.  Not a port: the reference has no DCD.  tests/dcd_ref.py restates all of this in numpy.
+ *   Input, dense, per cloud b of B: dist1 (B, n) fp32 and idx1 (B, n) int32, the squared distance and the index of the nearest of the
+ *     second set's m points for every point of the first set (what dpf_nndistance returns); dist2 (B, m), idx2 (B, m) the other way,
+ *     indices into the first set.  alpha > 0 and n_lambda >= 0, both finite; non_reg 0 or not.  Nothing is read but these.
+ *   Counts: c1[i] = the number of i' in [0, n) with idx1[i'] == idx1[i] (at least 1: i itself); c2[j] the same over idx2.  Exact.
+ *   Terms, float64, every operation rounded on its own (no contraction), for side 1 (side 2: n and m swapped, dist2, c2):
+ *       frac1 = (double) n / (double) m, under non_reg max(frac1, 1.0)
+ *       p = (double) c1[i] when n_lambda == 1;  1.0 when n_lambda == 0;  pow((double) c1[i], n_lambda) otherwise
+ *       W = frac1 / (p + 1e-6)          e = exp(-(alpha * (double) dist1[i]))          q = e * W          term[i] = 1.0 - q
+ *       coef1[i] = fp32( h1 * q ),  h1 = (0.5 * alpha) / (double) n
+ *     coef1[i] is d loss[b] / d dist1[i] with the weights W held constant, which is how the published loss detaches them.
+ *   Sums, ORDER as dpf_icp's: a block is 256 consecutive queries; its sum is the pairwise tree  for stride = 128, 64, ..., 1:
+ *     x[i] += x[i + stride]  over the block's terms (+0.0 past the end); the block sums are added in ascending block order starting
+ *     from block 0's: S1.  L1 = S1 / (double) n, L2 = S2 / (double) m, loss[b] = 0.5 * (L1 + L2).
+ *     exp and pow are the device library's (not correctly rounded): loss and halves are accurate to DCD_BOUND (tests/dcd_ref.py)
+ *     relative to max(1, frac1, frac2) for finite distances >= 0, bit-identical from run to run and between the two forms.
+ *   Refused: a cloud with an index outside [0, m) in idx1 or outside [0, n) in idx2.  It gets NaN in loss, halves and both coefs,
+ *     -1 in both counts and status DPF_DCD_REFUSED; such an index is never used as an address and no other cloud is touched.
+ *     Distances that are negative or not finite are NOT refused: they go through the arithmetic above.
+ *   Outputs, dense: loss (B) float64 and status (B) int32 (0 or DPF_DCD_REFUSED), both required; halves (B, 2) float64 = L1, L2;
+ *     count1 (B, n), count2 (B, m) int32; coef1 (B, n), coef2 (B, m) fp32 -- each of these optional (NULL: not written).
+ *   form: 0 by size (dispatch::dcd_form), 1 the one-workgroup form (counts in LDS, one launch; n, m <= 32768, DPF_ENOSUP above),
+ *     2 the workspace form (counts in the workspace: four launches).  The outputs do not depend on it.
+ *   Arguments: B < 0, n < 1, m < 1, an alpha that is not positive and finite, an n_lambda that is negative or not finite, an unknown
+ *     form, a missing required pointer, a workspace that is not 8-byte aligned or smaller than dpf_dcd_workspace_bytes(B, n, m)
+ *     return DPF_EINVAL; B == 0 launches nothing.  The workspace is caller-owned, may come in dirty and is left dirty.
+ *   The caller's stream, no allocation, no synchronisation, no memset node, no floating-point atomic (the counts are integer
+ *     atomics: order-independent); capture-safe.  Every loop runs over n, m or the block count. */
+#define DPF_DCD_REFUSED (-1)
+size_t dpf_dcd_workspace_bytes(int B, int n, int m);
+int dpf_dcd(int B, int n, int m, const float *dist1, const int *idx1, const float *dist2, const int *idx2, double alpha,
+            double n_lambda, int non_reg, int form, double *loss, double *halves, int *count1, int *count2, float *coef1,
+            float *coef2, int *status, void *workspace, size_t workspace_bytes, dpf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
