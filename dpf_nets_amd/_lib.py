@@ -147,6 +147,8 @@ SIGNATURES = {
     "dpf_align_workspace_bytes": (_sz, [_i, _i]),
     "dpf_rigid_fit": (_i, [_i, _i, _vp, _l, _l, _l, _vp, _l, _l, _l, _vp, _i] + [_vp] * 6 + [_vp, _sz, _vp]),
     "dpf_icp": (_i, [_i, _i, _vp, _l, _l, _l, _i, _vp, _l, _l, _l, _i, _f, _i] + [_vp] * 11 + [_vp, _sz, _vp]),
+    "dpf_icp_plane_workspace_bytes": (_sz, [_i, _i]),
+    "dpf_icp_plane": (_i, [_i, _i, _vp, _l, _l, _l, _i, _vp, _l, _l, _l, _vp, _i, _f, _d] + [_vp] * 13 + [_vp, _sz, _vp]),
     "dpf_dcd_workspace_bytes": (_sz, [_i, _i, _i]),
     "dpf_dcd": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _d, _d, _i, _i] + [_vp] * 7 + [_vp, _sz, _vp]),
     "dpf_version":(ctypes.c_char_p, []),

@@ -17,6 +17,14 @@
 //     quaternion.  The matrices are subscripted with compile-time indices only (unrolled pairs under a rolled sweep loop): they live
 //     in registers, and the Makefile refuses a build of these kernels that uses scratch.
 //
+// Point-to-plane ICP (dpf_icp_plane; tests/align_plane_ref.py restates it) is the same pair under the same launch pattern:
+//   * align_plane_match_kernel -- the body of align_match_kernel under another FORM: the scan, the tie rule, the trim, the changed
+//     count and the refusal are one text.  The lane then gathers its match's normal and adds thirty-one float64 terms (W, the upper
+//     triangle of sum a a^T for a = (y' x n ; n), sum a r, S_d, S_r, S_yy); the trees run in two batches of 16 over 32 KB of LDS.
+//   * align_plane_solve_kernel -- one wave per slot, lanes 0-30 the sums, lanes 31 and 32 the counts; lane 0 solves the damped 6 x 6
+//     normal equations by LDL^T without pivoting (a pivot that is not > 0 drops its unknown) and composes the increment, a unit
+//     quaternion, onto the transform.  Only + - * / sqrt; compile-time indices only.
+//
 // The current transform lives in the outputs R, t, s (iteration 0 reads the caller's init, or the identity); a slot's two flags --
 // done, refused -- in the workspace.  A done slot's later launches return on a block-uniform branch.  Iteration 0 takes "everything
 // changed" and "not done" from the argument k == 0, never from memory: nothing is cleared before the first launch.
@@ -38,9 +46,14 @@ constexpr int AL_Q = dispatch::ALIGN_SUMS;
 constexpr int AL_SWEEPS = dispatch::ALIGN_SWEEPS;
 constexpr int AL_GROUP = 4;                         // candidates per LDS read
 constexpr int AL_T = 13;                            // doubles of a packed transform: R row-major, t, s
+constexpr int AP_Q = dispatch::ALIGN_PLANE_SUMS;    // dpf_icp_plane: float64 quantities per slot
+constexpr int AP_BATCH = 16;                        // of them a pass of the tree takes: two passes, 32 KB of LDS
+constexpr int AP_MIN_INLIERS = dispatch::ALIGN_PLANE_MIN_INLIERS;
+enum { AL_ICP = 0, AL_GIVEN = 1, AL_PLANE = 2 };    // what a match launch reduces: dpf_icp, dpf_rigid_fit, dpf_icp_plane
 
 static_assert(AL_TILE == AL_THREADS && AL_TILE % AL_GROUP == 0, "one thread stages one candidate of a tile");
 static_assert((AL_THREADS & (AL_THREADS - 1)) == 0 && AL_Q <= 18, "the tree halves the block; lanes 0-17 own the sums");
+static_assert(AP_Q == 31 && AP_Q + 2 <= 64 && AP_BATCH <= AL_THREADS, "lanes 0-30 own the plane sums, lanes 31 and 32 the counts");
 
 struct AlignArgs {
     const float *src;
@@ -65,6 +78,14 @@ struct AlignArgs {
     long nblk;
 };
 
+// dpf_icp_plane: the same, and (with_scale 0, weights NULL, s written as 1; partial is (B, nblk, 31))
+struct PlaneArgs : AlignArgs {
+    const double *normals;                          // (B, m, 3) dense
+    double tol2;                                    // tol * tol
+    double *rmse_plane, *step;                      // (B, iters + 1) each
+    double *step2;                                  // workspace: (B): the squared step of the slot's last solve
+};
+
 // a coordinate, a transform entry or a weight the contract refuses: not finite, or larger in magnitude than 2^30 (NaN fails the comparison)
 __device__ __forceinline__ unsigned al_out_of_range(float x) { return (unsigned)!(__builtin_fabsf(x) <= 0x1p30f); }
 __device__ __forceinline__ unsigned al_out_of_range(double x) { return (unsigned)!(__builtin_fabs(x) <= 0x1p30); }
@@ -84,10 +105,16 @@ __device__ __forceinline__ void al_transform(const AlignArgs &A, size_t b, int k
     }
 }
 
-template <bool GIVEN>
-__global__ __launch_bounds__(AL_THREADS) void align_match_kernel(AlignArgs A, int k, int b0, long blk0) {
+// upper triangle of a symmetric 6 x 6 matrix, row-major: (0,0) (0,1) .. (0,5) (1,1) .. (5,5)
+__host__ __device__ constexpr int ap_tri(int i, int j) { return i * 6 - i * (i - 1) / 2 + (j - i); }
+
+// The body of a match launch.  FORM picks what follows the scan; the scan itself -- the transform, the distance, the tie rule, the
+// trim, the changed count, the refusal -- is one text for dpf_icp and dpf_icp_plane.
+template <int FORM, class Args>
+__device__ __forceinline__ void al_match_body(const Args &A, int k, int b0, long blk0) {
+    constexpr bool GIVEN = FORM == AL_GIVEN, PLANE = FORM == AL_PLANE;
     __shared__ __attribute__((aligned(16))) float tx[AL_TILE], ty[AL_TILE], tz[AL_TILE];
-    __shared__ double red[AL_Q][AL_THREADS];
+    __shared__ double red[PLANE ? AP_BATCH : AL_Q][AL_THREADS];
 
     const int tid = threadIdx.x, n = A.n, m = A.m;
     const size_t b = (size_t)b0 + blockIdx.y;
@@ -110,6 +137,13 @@ __global__ __launch_bounds__(AL_THREADS) void align_match_kernel(AlignArgs A, in
             }
         }
     }
+    if constexpr (PLANE) {                                                      // every normal of the slot: finite and above 2^30 refuses,
+        const double *N = A.normals + b * (size_t)m * 3;                        // not finite only takes its own match out
+        for (long u = tid; u < 3L * m; u += AL_THREADS) {
+            const double v = __builtin_fabs(N[u]);
+            bad |= (unsigned)(v > 0x1p30 && v < __builtin_inf());
+        }
+    }
     float px = 0.0f, py = 0.0f, pz = 0.0f;
     if (i < n) {
         const float *p = P + i * A.ssp;
@@ -118,6 +152,7 @@ __global__ __launch_bounds__(AL_THREADS) void align_match_kernel(AlignArgs A, in
 
     int idx = -1;
     float d = inf;
+    float yx = 0.0f, yy = 0.0f, yz = 0.0f;                                      // PLANE: the transformed point, kept for the terms
     if (!GIVEN) {
         double T[AL_T];
         al_transform(A, b, k, T);
@@ -127,6 +162,7 @@ __global__ __launch_bounds__(AL_THREADS) void align_match_kernel(AlignArgs A, in
             for (int e = 1; e < AL_T; ++e) mine = tid == e ? T[e] : mine;
             bad |= al_out_of_range(mine);
         }
+        if (PLANE && k == 0) bad |= (unsigned)!(T[12] == 1.0);                  // no scale is fitted: an init carries s = 1
         // y = fp32(s (R p) + t): float64, every operation rounded on its own, one rounding to fp32
         const double x = (double)px, y = (double)py, z = (double)pz;
         const float qx = (float)(((T[0] * x + T[1] * y) + T[2] * z) * T[12] + T[9]);
@@ -167,6 +203,7 @@ __global__ __launch_bounds__(AL_THREADS) void align_match_kernel(AlignArgs A, in
             }
         }
         if (usable && i < n) { idx = bj; d = best; }                            // (m >= 1 and every real distance is finite: bj >= 0)
+        if (PLANE) { yx = qx; yy = qy; yz = qz; }
         const bool trim = A.max_dist2 > 0.0f && A.max_dist2 < inf;
         if (trim && d > A.max_dist2) idx = -1;
     }
@@ -201,6 +238,60 @@ __global__ __launch_bounds__(AL_THREADS) void align_match_kernel(AlignArgs A, in
             qx = q[0]; qy = q[A.dsa]; qz = q[2 * A.dsa];
             w = 1.0;
         }
+    }
+    if constexpr (PLANE) {
+        // the target normal of the match; one that is not finite takes the pair out (weight 0) and leaves the index in place
+        double nv[3] = {0.0, 0.0, 0.0};
+        if (w > 0.0) {
+            const double *N = A.normals + (b * (size_t)m + (size_t)idx) * 3;
+            nv[0] = N[0]; nv[1] = N[1]; nv[2] = N[2];
+            const double inf64 = __builtin_inf();
+            if (!(__builtin_fabs(nv[0]) < inf64 && __builtin_fabs(nv[1]) < inf64 && __builtin_fabs(nv[2]) < inf64)) w = 0.0;
+        }
+        const bool inlier = w > 0.0;
+        // the thirty-one terms; +0.0 where there is no pair (and past n), and a zero term is +0.0 whatever the normal's sign
+        double term[AP_Q];
+#pragma unroll
+        for (int q = 0; q < AP_Q; ++q) term[q] = 0.0;
+        if (inlier) {
+            const double y[3] = {(double)yx, (double)yy, (double)yz};
+            const double yp[3] = {y[0] - (double)C[0], y[1] - (double)C[A.dsa], y[2] - (double)C[2 * A.dsa]};
+            const double r = (nv[0] * (y[0] - (double)qx) + nv[1] * (y[1] - (double)qy)) + nv[2] * (y[2] - (double)qz);
+            const double a[6] = {yp[1] * nv[2] - yp[2] * nv[1], yp[2] * nv[0] - yp[0] * nv[2], yp[0] * nv[1] - yp[1] * nv[0],
+                                 nv[0], nv[1], nv[2]};
+            term[0] = 1.0;
+#pragma unroll
+            for (int r0 = 0; r0 < 6; ++r0) {
+#pragma unroll
+                for (int c0 = r0; c0 < 6; ++c0) term[1 + ap_tri(r0, c0)] = a[r0] * a[c0] + 0.0;
+                term[22 + r0] = a[r0] * r + 0.0;
+            }
+            term[28] = (double)d;
+            term[29] = r * r;
+            term[30] = (yp[0] * yp[0] + yp[1] * yp[1]) + yp[2] * yp[2];
+        }
+        const int n_in = __syncthreads_count((int)inlier);
+        const int n_ch = __syncthreads_count(changed);
+        const size_t slot_blk = b * (size_t)A.nblk + (size_t)blk;
+#pragma unroll
+        for (int h = 0; h < AP_Q; h += AP_BATCH) {                              // the pairwise tree, AP_BATCH quantities a pass
+            if (h) __syncthreads();                                             // the pass before has been stored
+#pragma unroll
+            for (int q = 0; q < AP_BATCH; ++q)
+                if (h + q < AP_Q) red[q][tid] = term[h + q];
+            __syncthreads();
+            for (int stride = AL_THREADS / 2; stride >= 1; stride >>= 1) {
+                if (tid < stride) {
+#pragma unroll
+                    for (int q = 0; q < AP_BATCH; ++q)
+                        if (h + q < AP_Q) red[q][tid] = red[q][tid] + red[q][tid + stride];
+                }
+                __syncthreads();
+            }
+            if (tid < AP_BATCH && h + tid < AP_Q) A.partial[slot_blk * AP_Q + h + tid] = red[tid][0];
+        }
+        if (tid == 0) { A.count[slot_blk * 2] = n_in; A.count[slot_blk * 2 + 1] = n_ch; }
+        return;
     }
     const bool inlier = w > 0.0;
 
@@ -241,6 +332,15 @@ __global__ __launch_bounds__(AL_THREADS) void align_match_kernel(AlignArgs A, in
     if (tid == 0) { A.count[slot_blk * 2] = n_in; A.count[slot_blk * 2 + 1] = n_ch; }
 }
 
+template <bool GIVEN>
+__global__ __launch_bounds__(AL_THREADS) void align_match_kernel(AlignArgs A, int k, int b0, long blk0) {
+    al_match_body<GIVEN ? AL_GIVEN : AL_ICP>(A, k, b0, blk0);
+}
+
+__global__ __launch_bounds__(AL_THREADS) void align_plane_match_kernel(PlaneArgs A, int k, int b0, long blk0) {
+    al_match_body<AL_PLANE>(A, k, b0, blk0);
+}
+
 // One Jacobi rotation in the (P, Q) plane of the symmetric 4 x 4 matrix (both halves kept), normals.hip's formula; the columns P and Q
 // of the accumulated rotations turn the same way
 template <int P, int Q>
@@ -269,6 +369,15 @@ __device__ __forceinline__ void al_rotate(double (&a)[4][4], double (&v)[4][4]) 
         v[r][P] = c * x - s * y;
         v[r][Q] = s * x + c * y;
     }
+}
+
+// the rotation of the unit quaternion (q0; q1, q2, q3) = (w; x, y, z), the header's formula
+__device__ __forceinline__ void al_rotation(double q0, double q1, double q2, double q3, double (&R)[3][3]) {
+    const double ww = q0 * q0, xx = q1 * q1, yy = q2 * q2, zz = q3 * q3;
+    const double xy = q1 * q2, xz = q1 * q3, yz = q2 * q3, wx = q0 * q1, wy = q0 * q2, wz = q0 * q3;
+    R[0][0] = ((ww + xx) - yy) - zz; R[0][1] = 2.0 * (xy - wz);         R[0][2] = 2.0 * (xz + wy);
+    R[1][0] = 2.0 * (xy + wz);         R[1][1] = ((ww - xx) + yy) - zz; R[1][2] = 2.0 * (yz - wx);
+    R[2][0] = 2.0 * (xz - wy);         R[2][1] = 2.0 * (yz + wx);         R[2][2] = ((ww - xx) - yy) + zz;
 }
 
 // The closed form on a slot's sums: false where the slot is degenerate (T is then left as it was).  a, c: the pivots.
@@ -323,12 +432,8 @@ __device__ __forceinline__ bool al_solve(const double (&S)[AL_Q], int inliers, c
     if (__builtin_fabs(q3) > mag) pick = q3;
     if (pick < 0.0) { q0 = -q0; q1 = -q1; q2 = -q2; q3 = -q3; }
 
-    const double ww = q0 * q0, xx = q1 * q1, yy = q2 * q2, zz = q3 * q3;
-    const double xy = q1 * q2, xz = q1 * q3, yz = q2 * q3, wx = q0 * q1, wy = q0 * q2, wz = q0 * q3;
     double R[3][3];
-    R[0][0] = ((ww + xx) - yy) - zz; R[0][1] = 2.0 * (xy - wz);         R[0][2] = 2.0 * (xz + wy);
-    R[1][0] = 2.0 * (xy + wz);         R[1][1] = ((ww - xx) + yy) - zz; R[1][2] = 2.0 * (yz - wx);
-    R[2][0] = 2.0 * (xz - wy);         R[2][1] = 2.0 * (yz + wx);         R[2][2] = ((ww - xx) - yy) + zz;
+    al_rotation(q0, q1, q2, q3, R);
 
     // tr = sum_ab R_ab M_ba, row by row
     double tr = 0.0;
@@ -442,6 +547,159 @@ __global__ __launch_bounds__(64) void align_solve_kernel(AlignArgs A, int k, int
     state[0] = done;
 }
 
+// One Gauss-Newton step of point-to-plane on a slot's thirty-one sums: false where the slot is degenerate (T is then left as it was).
+// The damped normal equations A x = -b by LDL^T without pivoting, a pivot that is not > 0 dropping its unknown; the increment as a
+// unit quaternion, composed onto T about the pivot pc.  Every operation is one of + - * / sqrt, in the header's order; the matrices
+// are subscripted with compile-time indices only.
+__device__ __forceinline__ bool ap_solve(const double (&S)[AP_Q], int inliers, const double (&pc)[3], double (&T)[AL_T], double &step2) {
+    const double W = S[0];
+    if (inliers < AP_MIN_INLIERS || !(W > 0.0)) return false;
+    const double damp = 1.0 + 0x1p-40;
+    double D[6], L[6][6], x[6];
+    bool ok[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double d = S[1 + ap_tri(j, j)] * damp;
+#pragma unroll
+        for (int c = 0; c < j; ++c) d = d - (L[j][c] * L[j][c]) * D[c];
+        ok[j] = d > 0.0;
+        D[j] = ok[j] ? d : 0.0;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double e = S[1 + ap_tri(j, i)];
+#pragma unroll
+            for (int c = 0; c < j; ++c) e = e - (L[i][c] * L[j][c]) * D[c];
+            L[i][j] = ok[j] ? e / d : 0.0;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {                                               // L y = -b
+        double y = -S[22 + i];
+#pragma unroll
+        for (int c = 0; c < i; ++c) y = y - L[i][c] * x[c];
+        x[i] = ok[i] ? y : 0.0;
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) x[i] = ok[i] ? x[i] / D[i] : 0.0;               // D z = y
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {                                              // L^T x = z
+        double v = x[i];
+#pragma unroll
+        for (int c = i + 1; c < 6; ++c) v = v - L[c][i] * x[c];
+        x[i] = ok[i] ? v : 0.0;
+    }
+    // the increment: the unit quaternion (1; omega / 2) / norm
+    const double h0 = 0.5 * x[0], h1 = 0.5 * x[1], h2 = 0.5 * x[2];
+    const double norm = sqrt(((1.0 + h0 * h0) + h1 * h1) + h2 * h2);
+    double dR[3][3], R[3][3], tt[3];
+    al_rotation(1.0 / norm, h0 / norm, h1 / norm, h2 / norm, dR);
+    const double u[3] = {T[9] - pc[0], T[10] - pc[1], T[11] - pc[2]};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) R[a][c] = (dR[a][0] * T[c] + dR[a][1] * T[3 + c]) + dR[a][2] * T[6 + c];
+        tt[a] = (((dR[a][0] * u[0] + dR[a][1] * u[1]) + dR[a][2] * u[2]) + pc[a]) + x[3 + a];
+    }
+    const double s2 = ((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]) + ((x[3] * x[3] + x[4] * x[4]) + x[5] * x[5]) / (S[30] / W);
+    bool finite = __builtin_fabs(s2) < __builtin_inf();
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        finite = finite && __builtin_fabs(tt[a]) < __builtin_inf();
+#pragma unroll
+        for (int c = 0; c < 3; ++c) finite = finite && __builtin_fabs(R[a][c]) < __builtin_inf();
+    }
+    if (!finite) return false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) T[3 * a + c] = R[a][c];
+        T[9 + a] = tt[a];
+    }
+    step2 = s2;
+    return true;
+}
+
+// k: the iteration whose match is reduced; last: no solve follows (the match under the returned transform)
+__global__ __launch_bounds__(64) void align_plane_solve_kernel(PlaneArgs A, int k, int last, int b0) {
+    const int lane = threadIdx.x;
+    const size_t b = (size_t)b0 + blockIdx.y;
+    int *state = A.state + b * 2;
+    const size_t K1 = (size_t)A.iters + 1, at = b * K1 + k;
+    if (k > 0 && state[0]) {                                                    // done: the entries of this match repeat the last ones
+        if (lane == 0) {
+            A.rmse[at] = A.rmse[at - 1];
+            A.rmse_plane[at] = A.rmse_plane[at - 1];
+            A.step[at] = A.step[at - 1];
+            A.inliers[at] = A.inliers[at - 1];
+        }
+        return;
+    }
+    const int refused = state[1];
+    double acc = 0.0;
+    int cnt = 0;
+    if (!refused) {
+        const double *part = A.partial + b * (size_t)A.nblk * AP_Q;
+        const int *count = A.count + b * (size_t)A.nblk * 2;
+        if (lane < AP_Q) {
+            acc = part[lane];
+            for (long blk = 1; blk < A.nblk; ++blk) acc = acc + part[blk * AP_Q + lane];     // ascending block order
+        } else if (lane < AP_Q + 2) {
+            for (long blk = 0; blk < A.nblk; ++blk) cnt += count[blk * 2 + (lane - AP_Q)];
+        }
+    }
+    const double nan = __builtin_nan("");
+    if (A.sums && lane < AP_Q) A.sums[b * AP_Q + lane] = refused ? nan : acc;
+    double S[AP_Q];
+#pragma unroll
+    for (int q = 0; q < AP_Q; ++q) S[q] = __shfl(acc, q);
+    const int n_in = __shfl(cnt, AP_Q), n_ch = __shfl(cnt, AP_Q + 1);
+    if (lane != 0) return;
+
+    double *R = A.R + b * 9, *t = A.t + b * 3;
+    if (refused) {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) R[e] = nan;
+        t[0] = t[1] = t[2] = nan;
+        A.s[b] = nan;
+        A.rmse[at] = nan;
+        A.rmse_plane[at] = nan;
+        A.step[at] = nan;
+        A.inliers[at] = 0;
+        A.iterations[b] = 0;
+        A.status[b] = DPF_ALIGN_REFUSED;
+        state[0] = 1;
+        return;
+    }
+    double T[AL_T];
+    al_transform(A, b, k, T);
+    A.rmse[at] = sqrt(S[28] / S[0]);
+    A.rmse_plane[at] = sqrt(S[29] / S[0]);
+    A.inliers[at] = n_in;
+
+    int done = 0, status = 0;
+    bool solved = false;
+    double step2 = 0.0;
+    if (k > 0 && n_ch == 0 && A.step2[b] <= A.tol2) done = 1;                   // the matches stand and the step that led here was small
+    else if (last) done = 1;
+    else {
+        const float *C = A.dst + (long)b * A.dsc;
+        const double pc[3] = {(double)C[0], (double)C[A.dsa], (double)C[2 * A.dsa]};
+        solved = ap_solve(S, n_in, pc, T, step2);
+        if (!solved) { done = 1; status = DPF_ALIGN_DEGENERATE; }
+    }
+    A.step[at] = solved ? sqrt(step2) : 0.0;                                    // the step taken from this match: none where no solve follows
+    if (solved) A.step2[b] = step2;
+    if (k == 0 || solved) {                                                     // (a slot that keeps its transform past iteration 0 has it in place)
+#pragma unroll
+        for (int e = 0; e < 9; ++e) R[e] = T[e];
+        t[0] = T[9]; t[1] = T[10]; t[2] = T[11];
+        A.s[b] = 1.0;
+    }
+    if (k == 0 || status) A.status[b] = status;
+    if (done) A.iterations[b] = k;                                              // solves that gave the transform
+    state[0] = done;
+}
+
 size_t al_partial_bytes(int B, long nblk) { return (size_t)B * (size_t)nblk * AL_Q * sizeof(double); }
 size_t al_count_bytes(int B, long nblk) { return (size_t)B * (size_t)nblk * 2 * sizeof(int); }
 
@@ -505,5 +763,54 @@ extern "C" int dpf_icp(int B, int n, const float *src, long s_cloud_stride, long
     al_carve(A, B, workspace);
     for (int k = 0; k <= iters; ++k)
         if (const int e = al_round<false>(B, A, k, k == iters, (hipStream_t)stream)) return e;
+    return 0;
+}
+
+extern "C" size_t dpf_icp_plane_workspace_bytes(int B, int n) {
+    if (B < 1 || n < 1) return 0;
+    const long nblk = dispatch::align_plane_form(n, 0).blocks;
+    return (size_t)B * (size_t)nblk * AP_Q * sizeof(double) + (size_t)B * sizeof(double) + al_count_bytes(B, nblk) +
+           (size_t)B * 2 * sizeof(int);
+}
+
+extern "C" int dpf_icp_plane(int B, int n, const float *src, long s_cloud_stride, long s_point_stride, long s_axis_stride, int m,
+                             const float *dst, long d_cloud_stride, long d_point_stride, long d_axis_stride, const double *normals,
+                             int iters, float max_dist2, double tol, const double *init, double *R, double *t, double *s, int *index,
+                             float *dist, double *rmse, double *rmse_plane, double *step, int *inliers, int *iterations, double *sums,
+                             int *status, void *workspace, size_t workspace_bytes, dpf_stream_t stream) {
+    if (B < 0 || n < 1 || m < 1 || iters < 0 || !(tol >= 0.0)) return DPF_EINVAL;
+    if (B == 0) return 0;
+    if (!src || !dst || !normals || !R || !t || !s || !index || !dist || !rmse || !rmse_plane || !step || !inliers || !iterations ||
+        !status || !workspace || ((uintptr_t)workspace & 7))
+        return DPF_EINVAL;
+    if (workspace_bytes < dpf_icp_plane_workspace_bytes(B, n)) return DPF_EINVAL;
+    PlaneArgs A{};
+    static_cast<AlignArgs &>(A) = AlignArgs{src, s_cloud_stride, s_point_stride, s_axis_stride, dst, d_cloud_stride, d_point_stride,
+                                            d_axis_stride, nullptr, init, n, m, iters, 0, max_dist2, R, t, s, index, dist, rmse, inliers,
+                                            iterations, sums, status, nullptr, nullptr, nullptr,
+                                            dispatch::align_plane_form(n, iters).blocks};
+    A.normals = normals;
+    A.tol2 = tol * tol;
+    A.rmse_plane = rmse_plane;
+    A.step = step;
+    char *w = (char *)workspace;
+    const size_t pbytes = (size_t)B * (size_t)A.nblk * AP_Q * sizeof(double);
+    A.partial = (double *)w;
+    A.step2 = (double *)(w + pbytes);
+    A.count = (int *)(w + pbytes + (size_t)B * sizeof(double));
+    A.state = (int *)(w + pbytes + (size_t)B * sizeof(double) + al_count_bytes(B, A.nblk));
+    const hipStream_t st = (hipStream_t)stream;
+    for (int k = 0; k <= iters; ++k) {
+        if (const int e = dispatch::chunk_grid(B, A.nblk, [&](int b0, unsigned nb, long k0, unsigned nk) {
+                hipLaunchKernelGGL(align_plane_match_kernel, dim3(nk, nb), dim3(AL_THREADS), 0, st, A, k, b0, k0);
+                return (int)hipGetLastError();
+            }))
+            return e;
+        if (const int e = dispatch::chunk_grid(B, 1, [&](int b0, unsigned nb, long, unsigned) {
+                hipLaunchKernelGGL(align_plane_solve_kernel, dim3(1, nb), dim3(64), 0, st, A, k, k == iters ? 1 : 0, b0);
+                return (int)hipGetLastError();
+            }))
+            return e;
+    }
     return 0;
 }

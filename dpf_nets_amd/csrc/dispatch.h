@@ -435,6 +435,17 @@ inline AlignForm align_form(int n, int iters) {
     if (n < 1 || iters < 0) return {0, 0};
     return {ceil_div(n, ALIGN_WG_POINTS), 2 * ((long)iters + 1)};
 }
+// point-to-plane ICP (dpf_icp_plane): the same workgroups and the same launch pattern, thirty-one sums a block
+constexpr int ALIGN_PLANE_SUMS = 31;        // W, the upper triangle of sum a a^T (21), sum a r (6), S_d, S_r, S_yy
+constexpr int ALIGN_PLANE_MIN_INLIERS = 6;  // fewer planes than unknowns fix no step
+// blocks, launches: as AlignForm's; partial_doubles: the float64 block partials a slot keeps in the workspace.
+// Unserved (blocks 0): n < 1 or iters < 0.
+struct AlignPlaneForm { long blocks; long launches; long partial_doubles; };
+inline AlignPlaneForm align_plane_form(int n, int iters) {
+    if (n < 1 || iters < 0) return {0, 0, 0};
+    const long blocks = ceil_div(n, ALIGN_WG_POINTS);
+    return {blocks, 2 * ((long)iters + 1), blocks * ALIGN_PLANE_SUMS};
+}
 
 // ---- density-aware Chamfer distance (dcd.hip) ----------------------------------------------------------------------------------------
 constexpr int DCD_BLOCK = 256;            // queries of a block of the sums' tree (ALIGN_WG_POINTS: the same tree)

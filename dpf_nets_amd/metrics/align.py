@@ -1,5 +1,5 @@
-"""Rigid alignment on the device (dpf_rigid_fit, dpf_icp: include/dpf_hip.h; csrc/align.hip): the weighted Procrustes fit of given
-correspondences and trimmed point-to-point ICP -- what brings two clouds into one frame before Chamfer, F1 or an EMD compares them, so
+"""Rigid alignment on the device (dpf_rigid_fit, dpf_icp, dpf_icp_plane: include/dpf_hip.h; csrc/align.hip): the weighted Procrustes
+fit of given correspondences, trimmed point-to-point ICP and point-to-plane ICP -- what brings two clouds into one frame before Chamfer, F1 or an EMD compares them, so
 that those measure the shape and not the pose.  No (B, n, m) tensor, no host round trip per iteration, every output bit-identical
 from run to run.  Nothing the two searches return carries a gradient; a loss differentiates through apply_transform alone.  There is
 no CPU path."""
@@ -15,6 +15,7 @@ ALIGN_DEGENERATE, ALIGN_REFUSED = 1, -1
 
 RigidTransform = namedtuple("RigidTransform", ["R", "t", "s"])         # float64: (B, 3, 3), (B, 3), (B); y = s R p + t
 ICPInfo = namedtuple("ICPInfo", ["index", "dist", "rmse", "inliers", "iterations", "status"])
+PlaneICPInfo = namedtuple("PlaneICPInfo", ICPInfo._fields + ("rmse_plane", "step"))
 
 
 def _readable(points, channels_first, what, who):
@@ -41,17 +42,17 @@ def _pack(T, B, device, who):
     return torch.cat([R.reshape(B, 9), t, s[:, None]], dim=1).contiguous()
 
 
-def _report(status, who):
+def _report(status, who, refused="a coordinate, a weight or an entry of the initial transform is not finite or exceeds 2^30, or a weight "
+            "is negative", degenerate="fewer than 3 matched points, no weight or no spread"):
     """the one synchronisation: a refused slot raises, a degenerate one warns"""
     st = status.cpu()
     bad = torch.nonzero(st == ALIGN_REFUSED)
     if bad.numel():
-        raise ValueError("%s: slot %d of %d refused (a coordinate, a weight or an entry of the initial transform is not finite or exceeds "
-                         "2^30, or a weight is negative); %d refused in all" % (who, int(bad[0, 0]), st.numel(), bad.shape[0]))
+        raise ValueError("%s: slot %d of %d refused (%s); %d refused in all" % (who, int(bad[0, 0]), st.numel(), refused, bad.shape[0]))
     deg = torch.nonzero(st == ALIGN_DEGENERATE)
     if deg.numel():
-        warnings.warn("%s: slot %d of %d is degenerate (fewer than 3 matched points, no weight or no spread); it keeps the transform it "
-                      "had; %d degenerate in all" % (who, int(deg[0, 0]), st.numel(), deg.shape[0]), RuntimeWarning, stacklevel=3)
+        warnings.warn("%s: slot %d of %d is degenerate (%s); it keeps the transform it "
+                      "had; %d degenerate in all" % (who, int(deg[0, 0]), st.numel(), degenerate, deg.shape[0]), RuntimeWarning, stacklevel=3)
 
 
 def rigid_fit_raw(src, dst, weights=None, with_scale=False, channels_first=False, return_sums=False):
@@ -156,6 +157,79 @@ def icp(src, dst, iters=30, max_dist=None, with_scale=False, init=None, return_i
     if not return_info:
         return T
     return T, ICPInfo(out["index"].long(), out["dist"], out["rmse"], out["inliers"], out["iterations"], out["status"])
+
+
+def icp_plane_raw(src, dst, normals, iters=30, max_dist=None, tol=1e-7, init=None, channels_first=False, return_sums=False):
+    """dict of dpf_icp_plane's outputs (R, t, s, index int32, dist, rmse, rmse_plane, step, inliers, iterations, sums (B, 31) or None,
+    status): no look at the statuses, no synchronisation.  normals: a float CUDA tensor of shape (B, m, 3), always points-major."""
+    p, B, n, psc, psp, psa = _readable(src, channels_first, "source", "icp_plane")
+    q, Bq, m, qsc, qsp, qsa = _readable(dst, channels_first, "target", "icp_plane")
+    if Bq != B or q.device != p.device:
+        raise RuntimeError("icp_plane: source and target must share the batch size and the device, got %s and %s"
+                           % (tuple(src.shape), tuple(dst.shape)))
+    if not (torch.is_tensor(normals) and normals.is_cuda and normals.is_floating_point() and normals.device == p.device
+            and tuple(normals.shape) == (B, m, 3)):
+        raise RuntimeError("icp_plane: normals must be a floating-point CUDA tensor of shape (B, m, 3) = (%d, %d, 3) on the clouds' "
+                           "device; there is no CPU path" % (B, m))
+    iters = int(iters)
+    if iters < 0:
+        raise ValueError("icp_plane: iters must be >= 0, got %d" % iters)
+    if n < 1 or m < 1:
+        raise ValueError("icp_plane: no points")
+    if max_dist is not None and not float(max_dist) > 0:
+        raise ValueError("icp_plane: max_dist must be positive (None: no trim), got %r" % (max_dist,))
+    if not float(tol) >= 0:
+        raise ValueError("icp_plane: tol must be >= 0, got %r" % (tol,))
+    max_dist2 = 0.0 if max_dist is None else float(max_dist) ** 2
+    dev = p.device
+    nrm = normals.detach().to(torch.float64).contiguous()
+    T0 = _pack(init, B, dev, "icp_plane") if init is not None else None
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)          # noqa: E731
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)            # noqa: E731
+    out = dict(R=f64(B, 3, 3), t=f64(B, 3), s=f64(B), index=i32(B, n), dist=torch.empty((B, n), dtype=torch.float32, device=dev),
+               rmse=f64(B, iters + 1), rmse_plane=f64(B, iters + 1), step=f64(B, iters + 1), inliers=i32(B, iters + 1),
+               iterations=i32(B), sums=f64(B, 31) if return_sums else None, status=i32(B))
+    if B > 0:
+        with torch.cuda.device(dev):
+            nbytes = lib().dpf_icp_plane_workspace_bytes(B, n)
+            ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+            check(lib().dpf_icp_plane(B, n, p.data_ptr(), psc, psp, psa, m, q.data_ptr(), qsc, qsp, qsa, nrm.data_ptr(), iters, max_dist2,
+                                      float(tol), T0.data_ptr() if T0 is not None else None, out["R"].data_ptr(), out["t"].data_ptr(),
+                                      out["s"].data_ptr(), out["index"].data_ptr(), out["dist"].data_ptr(), out["rmse"].data_ptr(),
+                                      out["rmse_plane"].data_ptr(), out["step"].data_ptr(), out["inliers"].data_ptr(),
+                                      out["iterations"].data_ptr(), out["sums"].data_ptr() if return_sums else None,
+                                      out["status"].data_ptr(), ws.data_ptr(), nbytes, current_stream()), "icp_plane")
+    return out
+
+
+def icp_plane(src, dst, normals=None, k=16, iters=30, max_dist=None, tol=1e-7, init=None, return_info=False, channels_first=False):
+    """Point-to-plane ICP of src onto dst: RigidTransform(R, t, s) with s = 1, float64.  For two samplings of ONE surface -- a
+    decoder's samples against a ground-truth cloud -- where icp pulls every point toward a sample and stalls at a pose error set by
+    the sampling density, this pulls every point toward the target's tangent plane at its match.
+
+    src, dst, max_dist, init, channels_first and the match are icp's (init's scale must be 1).  normals (B, m, 3): one per target
+    point, any float dtype (converted to dense float64), used as given -- not normalised; their SIGN IS IRRELEVANT, bit for bit, so
+    estimate_normals' unoriented normals serve; None computes estimate_normals(dst, k) first (which synchronises once).  A normal with
+    a NaN takes its target point's matches out of the fit.  Every iteration solves the damped 6 x 6 normal equations of the linearised
+    distances and COMPOSES the increment (a proper rotation by construction) onto the transform.  A slot stops when no match changes
+    and the step before was at most tol (|omega|^2 + |tau|^2 / the mean squared extent, rooted); tol = 0 stops on an exactly zero
+    step only.  2 (iters + 1) launches, no synchronisation until the statuses are read.  A refused slot raises ValueError naming it;
+    a degenerate one (fewer than 6 matches) warns and keeps its transform.  A rank-deficient geometry (a planar target) is served:
+    the unknowns the data do not fix stay put.
+    return_info: also PlaneICPInfo -- ICPInfo's fields, then rmse_plane (B, iters + 1), the root mean square point-to-plane
+    residual per match, and step (B, iters + 1), the step taken from each match (0 where none was).  NO GRADIENT."""
+    if normals is None:
+        from .normals import estimate_normals
+        normals = estimate_normals(dst, k, channels_first=channels_first, double=True)[0]
+    out = icp_plane_raw(src, dst, normals, iters, max_dist, tol, init, channels_first)
+    _report(out["status"], "icp_plane",
+            "a coordinate or an entry of the initial transform is not finite or exceeds 2^30, the initial scale is not 1, or a finite "
+            "normal component exceeds 2^30", "fewer than 6 matched points with a finite normal")
+    T = RigidTransform(out["R"], out["t"], out["s"])
+    if not return_info:
+        return T
+    return T, PlaneICPInfo(out["index"].long(), out["dist"], out["rmse"], out["inliers"], out["iterations"], out["status"],
+                           out["rmse_plane"], out["step"])
 
 
 def apply_transform(T, clouds, channels_first=False):

@@ -1154,6 +1154,67 @@ int dpf_icp(int B, int n, const float *src, long s_cloud_stride, long s_point_st
             const double *init, double *R, double *t, double *s, int *index, float *dist, double *rmse, int *inliers,
             int *iterations, double *sums, int *status, void *workspace, size_t workspace_bytes, dpf_stream_t stream);
 
+/* Point-to-plane ICP (csrc/align.hip, dpf_icp_plane): dpf_icp's match with a Gauss-Newton step on the distances to the target's
+ * tangent planes in place of the closed form -- for two samplings of one surface, where point-to-point stalls at the sampling
+ * density.  tests/align_plane_ref.py restates all of this in numpy.  No scale is fitted (s = 1), no gradient.
+ *   Input: src, dst, the strides, max_dist2 and init as dpf_icp's; an init whose s entry is not exactly 1 refuses its slot.
+ *     normals (B, m, 3) float64 dense: one normal per target point, used AS GIVEN -- not normalised, and every output below is
+ *     unchanged, bit for bit, when any subset of them is negated (dpf_normals' unoriented normals are what it wants).
+ *     tol >= 0: the convergence threshold on the step (below).
+ *   Iteration k = 0 .. iters - 1: (1) MATCH as dpf_icp with s = 1 -- the bits of y = fp32(R p + t), the fp32 distance, the lowest
+ *     index among ties, the trim, changed and the 2^61 rule are dpf_icp's (one kernel text); (2) one SOLVE of the linearised problem
+ *     and the COMPOSITION of its increment onto the current transform.  After the last solve one more match runs under the returned
+ *     transform: index, dist, sums and the last rmse, rmse_plane and inliers belong to what is returned.  2 (iters + 1) launches.
+ *   Weights: a matched point has w = 1.  A trimmed match or a point with no match has index -1 and w = 0; a match j whose normal n_j
+ *     has a component that is not finite (the NaN dpf_normals writes for a flagged point) KEEPS index j and has w = 0.  inliers
+ *     counts w > 0; changed compares indices.
+ *   Terms of a pair with w = 1, float64, every operation rounded on its own; y and q = c_j are the fp32 values converted to float64,
+ *     c = target point 0 (the pivot), n = n_j:
+ *       y'_a = y_a - c_a        r = (n_0 (y_0 - q_0) + n_1 (y_1 - q_1)) + n_2 (y_2 - q_2)
+ *       a = (y'_1 n_2 - y'_2 n_1,  y'_2 n_0 - y'_0 n_2,  y'_0 n_1 - y'_1 n_0,  n_0, n_1, n_2)           (y' x n ; n)
+ *   Sums, thirty-one float64 quantities per slot, in this order:
+ *       [0] W = sum w        [1 + tri(i, j)] sum (a_i a_j + 0.0), i <= j, tri(i, j) = 6 i - i (i - 1) / 2 + (j - i): the upper
+ *       triangle of A = sum a a^T row-major, (0,0) (0,1) .. (0,5) (1,1) .. (5,5)        [22 + i] b_i = sum (a_i r + 0.0)
+ *       [28] S_d = sum (double) d        [29] S_r = sum r r        [30] S_yy = sum ((y'_0^2 + y'_1^2) + y'_2^2)
+ *     (the + 0.0 makes a zero product +0.0 whatever the normal's sign).  A pair with w = 0 contributes +0.0 to all of them.  ORDER:
+ *     dpf_icp's -- blocks of 256 consecutive points, the pairwise tree stride = 128 .. 1 (+0.0 past n), the block sums added in
+ *     ascending block order starting from block 0's.
+ *   Solve, float64, every operation one of + - * / sqrt, rounded on its own: A x = -b for x = (omega ; tau).
+ *       A_jj <- A_jj * (1 + 2^-40)                                            (Marquardt damping, scale-free)
+ *       LDL^T without pivoting, for j = 0 .. 5:
+ *         d = A_jj;  for c = 0 .. j - 1: d = d - (L_jc L_jc) D_c;     ok_j = d > 0;     D_j = ok_j ? d : 0
+ *         for i = j + 1 .. 5:  e = A_ji;  for c = 0 .. j - 1: e = e - (L_ic L_jc) D_c;     L_ij = ok_j ? e / d : 0
+ *       for i = 0 .. 5:   y_i = -b_i;  for c = 0 .. i - 1: y_i = y_i - L_ic y_c;     y_i = ok_i ? y_i : 0
+ *       z_i = ok_i ? y_i / D_i : 0
+ *       for i = 5 .. 0:   x_i = z_i;   for c = i + 1 .. 5: x_i = x_i - L_ci x_c;     x_i = ok_i ? x_i : 0
+ *     A pivot that is not > 0 drops its unknown (the rank-deficient case, such as a planar target: not an error).
+ *     Increment: h = 0.5 omega;  norm = sqrt(((1 + h_0 h_0) + h_1 h_1) + h_2 h_2);  the unit quaternion (1 / norm; h / norm) through
+ *     dpf_icp's quaternion-to-R formula gives dR, a proper rotation by construction that agrees with I + [omega]x to first order.
+ *       R_ab <- (dR_a0 R_0b + dR_a1 R_1b) + dR_a2 R_2b        u = t - c        t_a <- (((dR_a0 u_0 + dR_a1 u_1) + dR_a2 u_2) + c_a) + tau_a
+ *     Increments are COMPOSED (Gauss-Newton has no absolute solve).  |R^T R - I| <= |R0^T R0 - I| + 40 * 2^-53 per composition
+ *     (DESIGN 4.5k counts the operations).
+ *       step^2 = ((omega_0^2 + omega_1^2) + omega_2^2) + ((tau_0^2 + tau_1^2) + tau_2^2) / (S_yy / W)
+ *   Per match k: rmse[k] = sqrt(S_d / W), rmse_plane[k] = sqrt(S_r / W) (NaN where W = 0), inliers[k], and step[k] = sqrt(step^2) of
+ *     the solve that FOLLOWS match k -- 0 where none does (the last match, a converged or a degenerate slot).
+ *   Convergence: a slot is done when a match k > 0 finds changed == 0 and the solve before it had step^2 <= tol * tol; tol = 0 stops
+ *     only on an exactly zero step.  iterations = the number of solves that gave the transform; the entries of rmse, rmse_plane, step
+ *     and inliers after a done match repeat its values.
+ *   Degenerate: fewer than 6 inliers, W = 0, or a result (R, t or step^2) that is not finite.  The slot keeps its transform, gets
+ *     DPF_ALIGN_DEGENERATE and stops.  Refused: as dpf_icp, or an init s other than 1, or a FINITE normal component above 2^30 in
+ *     magnitude; the outputs are dpf_icp's for a refused slot, with NaN in rmse_plane and step.
+ *   Outputs, dense: R, t, s (written as 1), index, dist, rmse, inliers, iterations, status as dpf_icp's; rmse_plane and step
+ *     (B, iters + 1) float64; sums (B, 31) float64, optional (NULL: not written).
+ *   Arguments: as dpf_icp's; tol < 0 or NaN, a missing normals, rmse_plane or step, a workspace smaller than
+ *     dpf_icp_plane_workspace_bytes(B, n) return DPF_EINVAL.  The workspace need not be cleared.
+ *   Determinism and launches: as dpf_icp -- no memset node, no atomics, no synchronisation; a done slot returns on a block-uniform
+ *     branch; every loop runs over n, m, the block count or a compile-time count. */
+size_t dpf_icp_plane_workspace_bytes(int B, int n);
+int dpf_icp_plane(int B, int n, const float *src, long s_cloud_stride, long s_point_stride, long s_axis_stride, int m,
+                  const float *dst, long d_cloud_stride, long d_point_stride, long d_axis_stride, const double *normals, int iters,
+                  float max_dist2, double tol, const double *init, double *R, double *t, double *s, int *index, float *dist,
+                  double *rmse, double *rmse_plane, double *step, int *inliers, int *iterations, double *sums, int *status,
+                  void *workspace, size_t workspace_bytes, dpf_stream_t stream);
+
 /* ------------------------------------------------------------------------ *
  * Density-aware Chamfer distance (csrc/dcd.hip): DCD of Wu et al., "Balanced Chamfer Distance as a Comprehensive Metric for Point
  * Cloud Completion" (NeurIPS 2021), the published calc_dcd, from ONE nn_distance result per cloud: the counts, the loss and the

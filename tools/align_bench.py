@@ -6,6 +6,8 @@ Every step is a child process of its own under its own time limit (a step that e
     icp          metrics.icp at 32 x 2048 x 2048 and at 50 x 2500 x 2500 (the SVR evaluation shape), 30 iterations, from an 8 degree turn
     match        one match launch alone (dpf_icp with iters = 0) beside dpf_knn at k = 1 on the same clouds
     tensor_ops   the cdist / argmin / batched svd loop on the same inputs, 30 iterations
+    icp_plane    metrics.icp_plane beside metrics.icp on the same inputs, 30 iterations each, the target's normals (estimate_normals,
+                 k = 16) computed once outside the timed region: median, lowest and highest of --reps runs
 Times are medians of --reps runs after 3 warm-up runs, between two stream synchronisations."""
 import argparse
 import os
@@ -19,7 +21,7 @@ if ROOT not in sys.path:
 
 SHAPES = ((32, 2048, 2048), (50, 2500, 2500))
 ITERS = 30
-LIMITS = {"icp": 240, "match": 180, "tensor_ops": 300}
+LIMITS = {"icp": 240, "match": 180, "tensor_ops": 300, "icp_plane": 240}
 
 
 def clouds(B, n, m, seed=0):
@@ -34,7 +36,7 @@ def clouds(B, n, m, seed=0):
     return torch.from_numpy(src).to(dev), torch.from_numpy(dst.astype(np.float32)).to(dev)
 
 
-def median_ms(fn, reps):
+def sorted_ms(fn, reps):
     import torch
     for _ in range(3):
         fn()
@@ -46,6 +48,11 @@ def median_ms(fn, reps):
         torch.cuda.synchronize()
         times.append((time.perf_counter() - t0) * 1e3)
     times.sort()
+    return times
+
+
+def median_ms(fn, reps):
+    times = sorted_ms(fn, reps)
     return times[len(times) // 2]
 
 
@@ -71,7 +78,7 @@ def tensor_icp(src, dst, iters):
 def step(name, reps):
     import torch
     from dpf_nets_amd.metrics import icp
-    from dpf_nets_amd.metrics.align import icp_raw
+    from dpf_nets_amd.metrics.align import icp_raw, icp_plane_raw
     from dpf_nets_amd.metrics.knn import knn_index
     for B, n, m in SHAPES:
         src, dst = clouds(B, n, m)
@@ -89,6 +96,17 @@ def step(name, reps):
         elif name == "tensor_ops":
             ms = median_ms(lambda: tensor_icp(src, dst, ITERS), max(3, reps // 4))
             print("tensor_ops   %-16s %8.3f ms  cdist / argmin / batched svd, %d iterations, fp32, no early stop" % (shape, ms, ITERS))
+        elif name == "icp_plane":
+            from dpf_nets_amd.metrics import icp_plane, estimate_normals
+            nrm = estimate_normals(dst, 16, double=True)[0]
+            T, info = icp_plane(src, dst, nrm, iters=ITERS, return_info=True)
+            its = info.iterations.cpu().numpy()
+            a = sorted_ms(lambda: icp_plane_raw(src, dst, nrm, ITERS), reps)
+            b = sorted_ms(lambda: icp_raw(src, dst, ITERS), reps)
+            print("icp_plane    %-16s %8.3f ms  (low %.3f, high %.3f; %d iterations asked, tol 1e-7; the slots stopped after %d..%d; final "
+                  "rmse_plane %.2e);  icp on the same inputs: %8.3f ms (low %.3f, high %.3f)"
+                  % (shape, a[len(a) // 2], a[0], a[-1], ITERS, its.min(), its.max(), float(info.rmse_plane[:, -1].max()),
+                     b[len(b) // 2], b[0], b[-1]))
         else:
             raise SystemExit("unknown step " + name)
     print("device: " + torch.cuda.get_device_name(0))
@@ -103,7 +121,7 @@ def main():
     if args.step:
         return step(args.step, args.reps)
     lines = ["rigid alignment (csrc/align.hip): tools/align_bench.py, medians of %d runs" % args.reps]
-    for name in ("icp", "match", "tensor_ops"):
+    for name in ("icp", "match", "tensor_ops", "icp_plane"):
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", name, "--reps", str(args.reps)], capture_output=True,
                                text=True, timeout=LIMITS[name])
